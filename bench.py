@@ -12,15 +12,27 @@ EU/step is counted from the actual hierarchy.
 N GPUs: `bench.py --gpus N` starts N worker processes itself (one per GPU; or run it under
 torchrun with N ranks, whose WORLD_SIZE must equal --gpus): every rank trains on its own mesh of the same size (rotation seed = rank),
 one RCCL gradient all-reduce per step (bucketed, overlapped with the backward): weak scaling,
-value = total EU / max-rank time. The same run also measures the north-star scaling case,
-C4 strong scaling (BASELINE.json configs[3]: a fixed global batch of 64 ellipsoid(400,250)
-meshes split over the ranks), and reports it under "c4_strong" (disable: --no-c4).
+value = total EU / max-rank time.
 
 --config c4 makes C4 the headline instead; --config c5 --mode fwd is the HBM stress forward.
 
 Timing: W untimed warm-up steps, then K steps with NO instrumentation, bracketed by barrier +
-synchronize, max over ranks. A separate pass of --profile-steps steps (not timed for `value`)
-records HIP events around every libaerognn launch for the per-kernel table and the roofline.
+synchronize, max over ranks.
+
+A plain run does only that: set up, warm up, time the K steps, write the outputs if
+--dump-outputs is given, print the line. --full adds everything else the benchmark measures, in
+runs of their own after the timed steps (none of it changes `value`):
+* a pass of --profile-steps steps that records HIP events around every libaerognn launch, for the
+  per-kernel table ("kernels") and the roofline ("roofline");
+* the north-star scaling case, C4 strong scaling (BASELINE.json configs[3]: a fixed global batch
+  of 64 ellipsoid(400,250) meshes split over the ranks), under "c4_strong" (disable: --no-c4);
+* the CPU oracle's rate on a bounded sample, under "cpu_baseline" (disable: --no-cpu-baseline).
+
+--dump-outputs DIR writes what the last timed step computed, as rank 0's caller receives it, to
+DIR/<name>.npy in float32: `pred` (the model output, micro-batches concatenated), and after a
+train step `loss` and every parameter as the optimizer left it (`param.<state_dict key>`). At most
+64 MB in all: past that the largest array is cut to a fixed, seeded sample of its elements. The inputs
+and the initial weights are seeded, so two runs with the same arguments dump comparable arrays.
 
 Prints ONE JSON line (rank 0).
 """
@@ -318,6 +330,28 @@ def kernel_table(prof, steps, elapsed_step_s):
     return tab
 
 
+DUMP_BUDGET = 64 * 10**6  # bytes of array data under --dump-outputs DIR, all files together
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy (float32). When the arrays together exceed
+    DUMP_BUDGET, the largest is cut to a fixed sample of its elements (flat indices drawn without
+    replacement from numpy's default_rng(0), ascending), the same in every run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    header = 4096 * len(arrays)  # generous bound on the .npy headers
+    total = header + 4 * sum(t.numel() for t in arrays.values())
+    if total > DUMP_BUDGET:
+        big = max(arrays, key=lambda k: arrays[k].numel())
+        keep = (DUMP_BUDGET - (total - 4 * arrays[big].numel())) // 4
+        if keep <= 0:
+            raise SystemExit(f"bench: --dump-outputs: the arrays besides {big} alone exceed {DUMP_BUDGET} bytes")
+        idx = np.sort(np.random.default_rng(0).choice(arrays[big].numel(), size=keep, replace=False))
+        arrays[big] = arrays[big].reshape(-1)[torch.from_numpy(idx).to(arrays[big].device)]
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -377,9 +411,16 @@ def main():
     ap.add_argument("--mode", default="train", choices=["train", "fwd"])
     ap.add_argument("--model", default="bsms_mgn", choices=["bsms_mgn", "bsms_gnn"],
                     help="bsms_mgn: BiStridedMeshGraphNet (the headline); bsms_gnn: the stale BSMS_MeshGraphNet")
-    ap.add_argument("--profile-steps", type=int, default=1, help="extra instrumented steps for the kernel table")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c4", action="store_true", help="skip the secondary C4 strong-scaling measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the per-kernel table and the roofline "
+                         "(--profile-steps), the C4 strong-scaling leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; at most 64 MB)")
+    ap.add_argument("--profile-steps", type=int, default=1,
+                    help="--full: extra instrumented steps for the kernel table")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-c4", action="store_true",
+                    help="--full: skip the secondary C4 strong-scaling measurement")
     ap.add_argument("--strong-config", default=None, choices=sorted(BATCHED),
                     help="run the strong-scaling leg on this batched config (default: c4 after a c3 train run)")
     ap.add_argument("--cpu-plan", action="store_true", help="run BASELINE.md §3's full CPU plan and exit")
@@ -392,6 +433,8 @@ def main():
         return
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # one process per GPU, started here (the same run torchrun would make)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -467,19 +510,29 @@ def main():
         n_glob = D.global_count(sum(b["y"].numel() for b in batches), dev)
 
         def step():
+            preds, losses = [], []
             if args.mode == "train":
                 for i, b in enumerate(batches):  # gradient accumulation over micro-batches
                     if i == len(batches) - 1:
                         allreduce.arm()  # buckets all-reduce as their grads land (overlaps the backward)
-                    D.mse_sum_loss(fwd(b), b["y"], n_glob).backward()
+                    if last_step is None:
+                        D.mse_sum_loss(fwd(b), b["y"], n_glob).backward()
+                        continue
+                    preds.append(fwd(b))
+                    losses.append(D.mse_sum_loss(preds[-1], b["y"], n_glob))
+                    losses[-1].backward()
                 allreduce()
                 opt.step()
                 opt.zero_grad(set_to_none=True)
             else:
                 with torch.no_grad():
                     for b in batches:
-                        fwd(b)
+                        preds.append(fwd(b))
+            if last_step is not None:  # --dump-outputs: references only, no copy and no sync
+                last_step[:] = [preds, losses]
         return step
+
+    last_step = [] if args.dump_outputs and rank == 0 else None
 
     def timed_run(step, steps, warmup, per_rank=None):
         """Wall time of `steps` steps bracketed by barrier + synchronize, the MAX over ranks; with
@@ -528,9 +581,19 @@ def main():
         eu_all = int(t_eu.item())
     value = eu_all * args.steps / elapsed / 1e6
 
-    # instrumented pass (not part of `value`): HIP events around every libaerognn launch
+    if last_step is not None:  # before anything below runs further steps
+        preds, losses = last_step
+        arrays = {"pred": torch.cat([p.detach().reshape(-1, p.shape[-1]) for p in preds])}
+        if args.mode == "train":
+            arrays["loss"] = torch.stack([l.detach() for l in losses]).sum().reshape(1)
+            arrays.update({"param." + k: p.detach() for k, p in model.named_parameters()})
+        dump_outputs(args.dump_outputs, arrays)
+        last_step = None  # the steps of the --full legs keep nothing
+        del preds, losses, arrays
+
+    # --full: instrumented pass (not part of `value`): HIP events around every libaerognn launch
     kernels, roof = {}, None
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         core.PROF = []
         torch.cuda.synchronize()
         for _ in range(args.profile_steps):
@@ -538,7 +601,7 @@ def main():
         torch.cuda.synchronize()
         prof, core.PROF = core.PROF, None
         kernels = kernel_table(prof, args.profile_steps, step_s)
-    if args.model == "bsms_mgn":
+    if args.full and args.model == "bsms_mgn":
         B, F = 0.0, 0.0
         for b in batches:
             bb, ff = alg_step_cost(model, b, s_el, args.mode == "train")
@@ -553,7 +616,7 @@ def main():
     else:
         step_roof = None
     pmc = None
-    if args.traffic and os.path.exists(args.traffic) and args.config == "c3" and args.mode == "train" \
+    if args.full and args.traffic and os.path.exists(args.traffic) and args.config == "c3" and args.mode == "train" \
             and args.model == "bsms_mgn":
         pmc = json.load(open(args.traffic))
     if step_roof is not None and pmc and pmc.get("per_step_bytes"):
@@ -618,15 +681,16 @@ def main():
                    "edge_updates_per_step_per_gpu": eu_step, "edge_updates_per_step_all_ranks": eu_all,
                    "level_edges": Es,
                    "global_batch": extra.get("global_batch_meshes", ws), "parallelism": f"dp{ws}"},
-        "roofline": roof,
-        "kernels": kernels,
+        "full": args.full,
     }
+    if args.full:
+        out.update(roofline=roof, kernels=kernels)
     if D.active():
         out["collective"] = {"backend": torch.distributed.get_backend(), "world_size": ws,
                              "buckets": len(allreduce_ref[0].buckets) if allreduce_ref else None,
                              "launched_in_hooks": allreduce_ref[0].launched_in_hooks if allreduce_ref else None}
     strong = args.strong_config or ("c4" if args.config == "c3" else None)
-    if args.model == "bsms_mgn" and strong and args.mode == "train" and not args.no_c4:
+    if args.full and args.model == "bsms_mgn" and strong and args.mode == "train" and not args.no_c4:
         del model, batches, step
         torch.cuda.empty_cache()
         m4, b4, eu4, _, wl4, _, ex4 = setup(strong)
@@ -663,7 +727,7 @@ def main():
     from aerognn import _lib as L
     fault = L.fault_status(reset=False)
     out["fault_word"] = fault
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline and args.model == "bsms_mgn":
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu_baseline and args.model == "bsms_mgn":
         out["cpu_baseline"] = cpu_baseline(S)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -125,7 +125,7 @@ def test_bench_self_launch_two_ranks_json():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", AEROGNN_DIST_BACKEND="gloo", AEROGNN_MEMLOG="0")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--config", "small", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--strong-config", "c4small"], env=env, cwd=ROOT, capture_output=True,
+                        "--full", "--no-cpu-baseline", "--strong-config", "c4small"], env=env, cwd=ROOT, capture_output=True,
                        text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -6,7 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out
 export AEROGNN_MEMLOG=0
 T=$1; shift
-B="bench.py --no-cpu-baseline --no-c4 --steps 12 --warmup 3"
+B="bench.py --full --no-cpu-baseline --no-c4 --steps 12 --warmup 3"
 for rep in 1 2; do
   for L in "$@" cur; do
     n=$(basename $L .so)

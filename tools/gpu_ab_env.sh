@@ -10,7 +10,7 @@ MODES=${*:-train fwd}
 for rep in 1 2; do
   for val in $A $B; do
     for m in $MODES; do
-      env $V=$val timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-c4 --steps 12 --warmup 3 --mode $m \
+      env $V=$val timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-c4 --steps 12 --warmup 3 --mode $m \
         > gpurun_out/${T}_${V}${val}_${m}${rep}.log 2>&1
     done
   done

@@ -14,7 +14,7 @@ STEPS=${2:-3}
 R=$PWD
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$R"
-B="bench.py --no-cpu-baseline --no-c4"
+B="bench.py --full --no-cpu-baseline --no-c4"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$TAG -o c3 -- \
     python $B --steps $STEPS --warmup 1 > gpurun_out/prof_$TAG.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch_$TAG -o c3 -- \
