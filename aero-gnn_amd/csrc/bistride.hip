@@ -6,16 +6,13 @@
 // compactions (scan); WeightedEdgeConv sums walk CSC (by receiver) / CSR (by sender) groups in
 // edge order, and its parameter-gradient partials are reduced in a fixed order. No float atomics.
 #include "common.hpp"
+#include "host.hpp"
 #include "aerognn.h"
 
 using namespace agn;
 
 namespace {
 
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
 inline dim3 grid1(long n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
 
 // ------------------------------------------------------------------------------ BFS

@@ -3,6 +3,7 @@
 // meshes (train.py:50-51; torch_geometric Batch.from_data_list). The reference runs these in
 // Python on the host per mesh; here they are single passes over the device arrays.
 #include "common.hpp"
+#include "host.hpp"
 #include "aerognn.h"
 
 using namespace agn;
@@ -106,11 +107,6 @@ __global__ void collate_kernel(int B, int64_t ne, int64_t nn, const int64_t* __r
   if (t < nn) batch[t] = mesh_of(node_off, t);
 }
 
-inline int status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 }  // namespace
 
 extern "C" {
@@ -122,7 +118,7 @@ int agn_edge_features(int ne, int64_t e_total, int pdim, const int64_t* edge_ind
   if (ne == 0) return 0;
   hipLaunchKernelGGL(edge_features_kernel, dim3((ne + 255) / 256), dim3(256), 0, (hipStream_t)stream, ne, e_total,
                      pdim, edge_index, pos, pos_ld, perm, mean, std, out);
-  return status();
+  return launch_status();
 }
 
 int agn_normalize(int n, int k, const float* x, int ld, const float* mean, const float* std, float* out, int out_ld,
@@ -132,7 +128,7 @@ int agn_normalize(int n, int k, const float* x, int ld, const float* mean, const
   const long t = (long)n * k;
   hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, k, x,
                      ld, mean, std, out, out_ld, inverse);
-  return status();
+  return launch_status();
 }
 
 size_t agn_col_stats_temp_bytes(int n, int k) {
@@ -151,7 +147,7 @@ int agn_col_stats(int n, int k, const float* x, int ld, float* mean, float* std,
   hipLaunchKernelGGL(colfinish_kernel, dim3(1), dim3(256), 0, st, n, k, nb, part, m64, mean, std, eps, 0);
   hipLaunchKernelGGL(colsum64_kernel, dim3(nb), dim3(256), 0, st, n, k, x, ld, m64, part);
   hipLaunchKernelGGL(colfinish_kernel, dim3(1), dim3(256), 0, st, n, k, nb, part, m64, mean, std, eps, 1);
-  return status();
+  return launch_status();
 }
 
 int agn_collate(int B, int64_t ne, int64_t nn, const int64_t* edge_off, const int64_t* node_off, int64_t* edge_index,
@@ -161,7 +157,7 @@ int agn_collate(int B, int64_t ne, int64_t nn, const int64_t* edge_off, const in
   if (t == 0) return 0;
   hipLaunchKernelGGL(collate_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, ne, nn,
                      edge_off, node_off, edge_index, batch);
-  return status();
+  return launch_status();
 }
 
 }  // extern "C"

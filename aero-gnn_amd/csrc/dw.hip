@@ -10,6 +10,7 @@
 // plain ds_read_b32. Per-chunk partials go to a slab and a second kernel sums the slabs in
 // fixed order: deterministic, no atomics.
 #include "common.hpp"
+#include "host.hpp"
 #include "aerognn.h"
 
 #include <type_traits>
@@ -384,11 +385,6 @@ __global__ __launch_bounds__(64 * RED_G) void colsum_stage2(const float* __restr
   }
 }
 
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 }  // namespace
 
 extern "C" {
@@ -397,12 +393,10 @@ namespace {
 int wgrad_resident() {
   static int resident = 0;
   if (resident == 0) {
-    int dev = 0, ncu = 256, per = 3;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ncu = p.multiProcessorCount;
+    int per = 3;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, wgrad_kernel<bf16, false>, DW_THREADS, 0) != hipSuccess || per < 1)
       per = 3;
-    resident = ncu * per;
+    resident = cu_count() * per;
   }
   return resident;
 }

@@ -26,18 +26,15 @@
 // wave streaming 32-row tiles in CSC order over an XCD-grouped walk; a tile's node ids are loaded
 // one tile ahead through the wave's LDS slot (a loop-carried load result would make the compiler
 // wait vmcnt(0) at the loop head, i.e. for the previous tile's stores too).
-#include "common.hpp"
+#include "tile32.hpp"
 #include "aerognn.h"
 
 using namespace agn;
+using namespace agn::t32;
 
 namespace {
 
-constexpr int H = 128;
-constexpr int NT = 4;                   // 32-feature output tiles
-constexpr int NR = 64;                  // acc registers per lane (features of the lane's row half)
-constexpr int NU = 8;                   // k-steps of 16 per layer
-constexpr int LAYER = NT * NU * 64;     // packed units (16 B) per weight image
+constexpr int LAYER = LAYER_UNITS;      // packed units (16 B) per weight image
 #ifndef AGN_E32_PF
 #define AGN_E32_PF 2
 #endif
@@ -55,39 +52,10 @@ struct Smem {
 };
 static_assert(sizeof(Smem) <= 160 * 1024, "LDS budget");
 
-// acc[ot] += W[ot tile] . b over k-steps u = 0..7 in order (the resident kernel's per-accumulator
-// sequence: common.hpp gemm); fragments (u, ot) stream PF deep, ot inner
+// Lin l's product: the resident kernel's per-accumulator sequence, fragments PF deep (tile32.hpp)
 AGN_DEV void gemm4(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* w, int lane) {
-  uint4 f[PF];
-#pragma unroll
-  for (int i = 0; i < PF; ++i) f[i] = w[((i % NT) * NU + i / NT) * 64 + lane];
-#pragma unroll
-  for (int idx = 0; idx < NT * NU; ++idx) {
-    const uint4 cur = f[idx % PF];
-    const int nx = idx + PF;
-    if (nx < NT * NU) f[idx % PF] = w[((nx % NT) * NU + nx / NT) * 64 + lane];
-    b.mfma(acc[idx % NT], cur, idx / NT);
-  }
+  gemm_stream<PF>(acc, b, w, NU, 0, 0, lane);
 }
-
-// XCD-aware walk (mlp.hip ResTiles): blocks b and b + 8 share an XCD and its L2, so each group of
-// blocks {g, g + 8, ...} walks one contiguous eighth of the tiles
-struct Walk {
-  int first, end, step;
-  AGN_DEV Walk(int ntiles, int w, int nw) {
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-      const int g = blockIdx.x & 7, bi = blockIdx.x >> 3, nb = gridDim.x >> 3;
-      const int per = (ntiles + 7) / 8;
-      first = g * per + bi * nw + w;
-      end = min(ntiles, (g + 1) * per);
-      step = nb * nw;
-    } else {
-      first = blockIdx.x * nw + w;
-      end = ntiles;
-      step = gridDim.x * nw;
-    }
-  }
-};
 
 // Diagnostic phase clocks (built with -DAGN_E32_STAMPS into a separate library only,
 // tools/e32_stamps.py): the waves of block 0 record s_memtime at 8 points of their first 16 tiles
@@ -183,17 +151,13 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
       if constexpr (SAVE) {  // a1 (AGN_TILED); behind Lin1's MFMAs or non-temporal: no faster (round 6)
         if (l == 1) b.store_tiled(reinterpret_cast<bf16*>(a.act[0]), row, h, valid);
       }
-#pragma unroll
-      for (int q = 0; q < 4 * NT; ++q) {  // acc = bias of Linear l (mlp.hip acc_bias_lds)
-        const f32x4 x = *reinterpret_cast<const f32x4*>(&sm.pv[l - 1][8 * q + 4 * h]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[q / 4][4 * (q % 4) + e] = x[e];
-      }
+      acc_bias(acc, sm.pv[l - 1], h);  // the bias of Linear l
       gemm4(acc, b, sm.w + l * LAYER, lane);
       E32_STAMP(2 + l);
     }
     cbarrier();
     // LayerNorm statistics over the row's 128 features (two lanes per row), resident kernel order
+    // (written out: as a shared helper the 63 adds below come out with their operands swapped)
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < (AGN_E32_DIAG == 1 ? 1 : NR); ++i) s += acc[i / 16][i % 16];
@@ -216,20 +180,11 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
       float v[NR];
 #pragma unroll
       for (int i = 0; i < NR / 8; ++i) {
+        float v8[8];
+        acc_get8(v8, acc, i);
+        ln_out8(v8, sm.pv[3], sm.pv[4], i, h, mean, rstd);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int f0 = 16 * i + 8 * j + 4 * h;
-          const f32x4 g4 = *reinterpret_cast<const f32x4*>(&sm.pv[3][f0]);
-          const f32x4 b4 = *reinterpret_cast<const f32x4*>(&sm.pv[4][f0]);
-#pragma unroll
-          for (int e = 0; e < 4; e += 2) {
-            const int r = 8 * i + 4 * j + e;
-            const f32x2 o = ln_out2(f2(acc[r / 16][r % 16], acc[(r + 1) / 16][(r + 1) % 16]), mean, rstd,
-                                    f2(g4[e], g4[e + 1]), f2(b4[e], b4[e + 1]));
-            v[r] = o[0];
-            v[r + 1] = o[1];
-          }
-        }
+        for (int e = 0; e < 8; ++e) v[8 * i + e] = v8[e];
       }
       BOp<bf16, NR> lnb;
       lnb.set(v);
@@ -240,8 +195,7 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
 #pragma unroll
     for (int i = 0; i < NR / 8; ++i) {
       float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = acc[(8 * i + e) / 16][(8 * i + e) % 16];
+      acc_get8(v, acc, i);
       store8_w(op, i, h, v, valid);
     }
 
@@ -251,24 +205,6 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
 #endif
   }
 }
-
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
-int g_cus = 0;
-int cu_count() {
-  if (g_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) g_cus = pr.multiProcessorCount;
-    if (g_cus <= 0) g_cus = 256;
-  }
-  return g_cus;
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -281,12 +217,7 @@ int agn_debug_e32_stamps(void* p) {
 #endif
 
 int agn_edge_fwd32_blocks(int rows) {
-  const int cus = cu_count();
-  const int tiles = (rows + 31) / 32;
-  const int need = (tiles + NW - 1) / NW;
-  if (need >= cus) return cus;
-  const int n = (need + 7) / 8 * 8;
-  return n < 8 ? 8 : n;
+  return tile_blocks((rows + 31) / 32, NW);
 }
 
 int agn_edge_forward32(const agn_edge_fwd_args* a, void* stream) {

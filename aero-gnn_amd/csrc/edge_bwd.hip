@@ -32,16 +32,14 @@
 // order the hand-offs, no workgroup barrier runs inside the main loops.
 // Per-workgroup partials (dW, db, LayerNorm) go to slabs that agn_wgrad_reduce / agn_colsum sum in
 // fixed order: no atomics on HBM.
-#include "common.hpp"
+#include "tile32.hpp"
 #include "aerognn.h"
 
 using namespace agn;
+using namespace agn::t32;
 
 namespace {
 
-constexpr int H = 128;
-constexpr int NT = 4;                  // 32-feature tiles per row
-constexpr int NR = 64;                 // acc registers per row half
 constexpr int CW = 4;                  // chain waves
 constexpr int NWAVE = 8;               // chain + dW waves
 constexpr int NTHR = 64 * NWAVE;
@@ -149,17 +147,7 @@ AGN_DEV void gemm_cols(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const char* im
 // Fragments stream PFG deep (L2 latency under the MFMAs).
 constexpr int PFG = 8;
 AGN_DEV void gemm_rows_g(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* w, int lane) {
-  uint4 f[PFG];
-#pragma unroll
-  for (int i = 0; i < PFG; ++i) f[i] = w[((i & 3) * 8 + (i >> 2)) * 64 + lane];
-#pragma unroll
-  for (int idx = 0; idx < 8 * NT; ++idx) {
-    const uint4 cur = f[idx % PFG];
-    const int nx = idx + PFG;
-    if (nx < 8 * NT) f[idx % PFG] = w[((nx & 3) * 8 + (nx >> 2)) * 64 + lane];
-    b.mfma(acc[idx & 3], cur, idx >> 2);
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  gemm_stream<PFG, true>(acc, b, w, NU, 0, 0, lane);
 }
 AGN_DEV void gemm_cols_g(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* wt, int lane) {
   uint4 f[PFG];
@@ -173,16 +161,6 @@ AGN_DEV void gemm_cols_g(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4*
     if (idx < NT) acc[idx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur, b.u[0], f32x16{}, 0, 0, 0);
     else mfma(acc[idx & 3], cur, b.u[idx >> 2]);
     __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// acc = bias (fp32 [H] in LDS), acc layout
-AGN_DEV void acc_bias(f32x16 (&acc)[NT], const float* pv, int h) {
-#pragma unroll
-  for (int q = 0; q < 4 * NT; ++q) {
-    const f32x4 x = *reinterpret_cast<const f32x4*>(pv + 8 * q + 4 * h);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[q / 4][4 * (q % 4) + e] = x[e];
   }
 }
 
@@ -222,7 +200,10 @@ AGN_DEV int fresh_lane(int lane) {
   return lane;
 }
 
-struct Rounds {  // XCD-grouped round walk (blocks b and b + 8 share an XCD and its L2)
+// The XCD-grouped walk of tile32.hpp over rounds, the block walking as one (Walk with nw = 1, w = 0).
+// Kept as a copy: through Walk, whose statements stand in another order, the scalar prologue of
+// every kernel here is scheduled differently.
+struct Rounds {
   int first, end, step;
   AGN_DEV Rounds(int nrounds) {
     if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
@@ -922,28 +903,12 @@ __global__ __launch_bounds__(NTHR, 2) void edge_bwd_fused_kernel(const agn_edge_
   }
 }
 
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
-int g_cus = 0;
-
 }  // namespace
 
 extern "C" {
 
 int agn_edge_bwd_blocks(int rows) {
-  if (g_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) g_cus = pr.multiProcessorCount;
-    if (g_cus <= 0) g_cus = 256;
-  }
-  const int rounds = ((rows + 31) / 32 + CW - 1) / CW;
-  if (rounds >= g_cus) return g_cus;
-  const int n = (rounds + 7) / 8 * 8;
-  return n < 8 ? 8 : n;
+  return tile_blocks((rows + 31) / 32, CW);
 }
 
 size_t agn_edge_bwd_scratch_bytes(int nblk) { return nblk > 0 ? (size_t)nblk * CW * 32 * H * 2 : 0; }

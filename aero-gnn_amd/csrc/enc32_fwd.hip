@@ -9,19 +9,16 @@
 // Why: the general kernel restages the three weight images into LDS for every 128-row block,
 // which on a 6M-row edge encoder costs more than the rows' own traffic (8 B in, 256 B out). Here
 // they stay resident (4 + 32 (L - 1) KB) and 16 waves per CU stream 32-row tiles.
-#include "common.hpp"
+#include "tile32.hpp"
 #include "aerognn.h"
 
 using namespace agn;
+using namespace agn::t32;
 
 namespace {
 
-constexpr int H = 128;
-constexpr int NT = 4;
-constexpr int NR = 64;
-constexpr int NU = 8;
 constexpr int LW0 = NT * 64;          // W0: one k-step unit per output tile (K <= 16)
-constexpr int LW = NT * NU * 64;      // W1 .. W_{L-1}
+constexpr int LW = LAYER_UNITS;       // W1 .. W_{L-1}
 constexpr int NW = 16;
 constexpr int PF = 2;
 
@@ -32,35 +29,13 @@ template <int NLIN> struct Smem {
 };
 static_assert(sizeof(Smem<4>) <= 160 * 1024, "LDS budget");
 
+// a hidden Linear's product from its resident image (tile32.hpp gemm_stream)
 AGN_DEV void gemm_k8(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* w, int lane) {
-  uint4 f[PF];
-#pragma unroll
-  for (int i = 0; i < PF; ++i) f[i] = w[((i % NT) * NU + i / NT) * 64 + lane];
-#pragma unroll
-  for (int idx = 0; idx < NT * NU; ++idx) {
-    const uint4 cur = f[idx % PF];
-    const int nx = idx + PF;
-    if (nx < NT * NU) f[idx % PF] = w[((nx % NT) * NU + nx / NT) * 64 + lane];
-    b.mfma(acc[idx % NT], cur, idx / NT);
-  }
+  gemm_stream<PF>(acc, b, w, NU, 0, 0, lane);
 }
 
-struct Walk {
-  int first, end, step;
-  AGN_DEV Walk(int ntiles, int w, int nw = NW) {
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-      const int g = blockIdx.x & 7, bi = blockIdx.x >> 3, nb = gridDim.x >> 3;
-      const int per = (ntiles + 7) / 8;
-      first = g * per + bi * nw + w;
-      end = min(ntiles, (g + 1) * per);
-      step = nb * nw;
-    } else {
-      first = blockIdx.x * nw + w;
-      end = ntiles;
-      step = gridDim.x * nw;
-    }
-  }
-};
+// The bias loops, the LayerNorm statistics and the save blocks of these kernels stay written out:
+// behind shared helpers (tile32.hpp acc_bias and the like) their instruction streams change.
 
 // SAVES: relu outputs act[l] (+ AGN_RELU_MASK bits), hpre, stats, as the general kernel writes them
 template <int NLIN, bool SAVES>
@@ -84,7 +59,7 @@ __global__ __launch_bounds__(64 * NW) void enc32_fwd_kernel(const agn_mlp_fwd_ar
   const int lane0 = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntiles = (a.rows + 31) / 32;
-  const Walk walk(ntiles, w);
+  const Walk walk(ntiles, w, NW);
   const agn_seg& sx = a.seg[0];
   const bf16* X = reinterpret_cast<const bf16*>(sx.ptr);
   for (int tile = walk.first; tile < walk.end; tile += walk.step) {
@@ -171,21 +146,8 @@ __global__ __launch_bounds__(64 * NW) void enc32_fwd_kernel(const agn_mlp_fwd_ar
 #pragma unroll
     for (int i = 0; i < NR / 8; ++i) {
       float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = acc[(8 * i + e) / 16][(8 * i + e) % 16];
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        const int f0 = 16 * i + 8 * jj + 4 * h;
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(&sm.pv[NLIN][f0]);
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(&sm.pv[NLIN + 1][f0]);
-#pragma unroll
-        for (int e = 0; e < 4; e += 2) {
-          const f32x2 o = ln_out2(f2(v[4 * jj + e], v[4 * jj + e + 1]), mean, rstd, f2(g4[e], g4[e + 1]),
-                                  f2(b4[e], b4[e + 1]));
-          v[4 * jj + e] = o[0];
-          v[4 * jj + e + 1] = o[1];
-        }
-      }
+      acc_get8(v, acc, i);
+      ln_out8(v, sm.pv[NLIN], sm.pv[NLIN + 1], i, h, mean, rstd);
       store8_w(op, i, h, v, valid);
     }
   }
@@ -272,19 +234,6 @@ __global__ __launch_bounds__(64 * DNW) void dec32_fwd_kernel(const agn_mlp_fwd_a
   }
 }
 
-int g_cus = 0;
-int cu_count() {
-  if (g_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) g_cus = pr.multiProcessorCount;
-    if (g_cus <= 0) g_cus = 256;
-  }
-  return g_cus;
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 long g_launches = 0;
 long g_dec_launches = 0;
 
@@ -313,11 +262,7 @@ bool enc32_fwd_try(const agn_mlp_fwd_args* a, void* stream, int* rc) {
   if (!al16(a->hpre)) return false;
   for (int l = 0; l < a->nlin; ++l)
     if (!a->wpk[l] || !al16(a->wpk[l])) return false;
-  const int tiles = (a->rows + 31) / 32;
-  const int need = (tiles + NW - 1) / NW;
-  const int cus = cu_count();
-  const int nblk = need >= cus ? cus : ((need + 7) / 8 * 8 < 8 ? 8 : (need + 7) / 8 * 8);
-  const dim3 g(nblk), blk(64 * NW);
+  const dim3 g(tile_blocks((a->rows + 31) / 32, NW)), blk(64 * NW);
   hipStream_t st = (hipStream_t)stream;
   if (a->nlin == 4) {
     if (saves) hipLaunchKernelGGL((enc32_fwd_kernel<4, true>), g, blk, 0, st, *a);
@@ -327,8 +272,7 @@ bool enc32_fwd_try(const agn_mlp_fwd_args* a, void* stream, int* rc) {
     else hipLaunchKernelGGL((enc32_fwd_kernel<3, false>), g, blk, 0, st, *a);
   }
   ++g_launches;
-  const hipError_t e = hipGetLastError();
-  *rc = e == hipSuccess ? 0 : (int)e;
+  *rc = launch_status();
   return true;
 }
 // the decoder: agn_mlp_forward's narrow-output calls (M_NOUT) this kernel covers
@@ -349,11 +293,7 @@ bool dec32_fwd_try(const agn_mlp_fwd_args* a, void* stream, int* rc) {
   for (int l = 0; l < a->nlin; ++l)
     if (!a->wpk[l] || !al16(a->wpk[l])) return false;
   const int dnw = saves ? 12 : 16;
-  const int tiles = (a->rows + 31) / 32;
-  const int need = (tiles + dnw - 1) / dnw;
-  const int cus = cu_count();
-  const int nblk = need >= cus ? cus : ((need + 7) / 8 * 8 < 8 ? 8 : (need + 7) / 8 * 8);
-  const dim3 g(nblk);
+  const dim3 g(tile_blocks((a->rows + 31) / 32, dnw));
   hipStream_t st = (hipStream_t)stream;
   if (saves) {
     if (a->nlin == 4) hipLaunchKernelGGL((dec32_fwd_kernel<4, true, 12>), g, dim3(64 * 12), 0, st, *a);
@@ -363,8 +303,7 @@ bool dec32_fwd_try(const agn_mlp_fwd_args* a, void* stream, int* rc) {
     else hipLaunchKernelGGL((dec32_fwd_kernel<3, false, 16>), g, dim3(64 * 16), 0, st, *a);
   }
   ++g_dec_launches;
-  const hipError_t e = hipGetLastError();
-  *rc = e == hipSuccess ? 0 : (int)e;
+  *rc = launch_status();
   return true;
 }
 }  // namespace agn

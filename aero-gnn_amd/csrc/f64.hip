@@ -8,14 +8,12 @@
 //                      parameter-gradient reduction
 // Everything is deterministic (no atomics).
 #include "common.hpp"
+#include "host.hpp"
 #include "aerognn.h"
 
-namespace {
+using agn::launch_status;
 
-inline int status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
+namespace {
 
 // ------------------------------------------------------------------------------ GEMM
 constexpr int GT = 64;   // output tile edge
@@ -339,7 +337,7 @@ int agn_f64_gemm(const agn_f64_gemm_args* a, void* stream) {
   if (a->rows == 0) return 0;
   const dim3 grid((a->rows + GT - 1) / GT, (a->n + GT - 1) / GT);
   hipLaunchKernelGGL(f64_gemm_kernel, grid, dim3(GTHR), 0, (hipStream_t)stream, *a);
-  return status();
+  return launch_status();
 }
 
 size_t agn_f64_wgrad_scratch_bytes(const agn_f64_wgrad_args* a) {
@@ -356,7 +354,7 @@ int agn_f64_wgrad(const agn_f64_wgrad_args* a, void* scratch, void* stream) {
     for (int m = 0; m < a->m; ++m)
       if (hipMemsetAsync(a->dw + (size_t)m * a->ldw, 0, sizeof(double) * a->k, st) != hipSuccess) return AGN_E_ARG;
     if (a->db && hipMemsetAsync(a->db, 0, sizeof(double) * a->m, st) != hipSuccess) return AGN_E_ARG;
-    return status();
+    return launch_status();
   }
   if (!scratch) return AGN_E_ARG;
   int mb, kb, ns, per;
@@ -367,7 +365,7 @@ int agn_f64_wgrad(const agn_f64_wgrad_args* a, void* scratch, void* stream) {
   const long tot = (long)a->m * a->k + (a->db ? a->m : 0);
   hipLaunchKernelGGL(f64_wgrad_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, *a, ns, mb * GT, kb * GT,
                      part, bpart);
-  return status();
+  return launch_status();
 }
 
 int agn_f64_layernorm_fwd(int rows, int n, const double* x, int ldx, const double* gamma, const double* beta,
@@ -377,7 +375,7 @@ int agn_f64_layernorm_fwd(int rows, int n, const double* x, int ldx, const doubl
   if (rows == 0) return 0;
   hipLaunchKernelGGL(f64_ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, rows, n, x, ldx,
                      gamma, beta, resid, ldr, y, ldy, mean, rstd, eps);
-  return status();
+  return launch_status();
 }
 
 size_t agn_f64_layernorm_bwd_scratch_bytes(int rows, int n) {
@@ -393,7 +391,7 @@ int agn_f64_layernorm_bwd(int rows, int n, const double* dy, int lddy, const dou
   if (rows == 0) {
     if (dgamma && hipMemsetAsync(dgamma, 0, sizeof(double) * n, st) != hipSuccess) return AGN_E_ARG;
     if (dbeta && hipMemsetAsync(dbeta, 0, sizeof(double) * n, st) != hipSuccess) return AGN_E_ARG;
-    return status();
+    return launch_status();
   }
   if (pgrad && !scratch) return AGN_E_ARG;
   const int nblk = (rows + LN_RB - 1) / LN_RB;
@@ -402,7 +400,7 @@ int agn_f64_layernorm_bwd(int rows, int n, const double* dy, int lddy, const dou
   if (pgrad)
     hipLaunchKernelGGL(f64_colsum_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, st,
                        reinterpret_cast<const double*>(scratch), nblk, 2 * n, dgamma, dbeta, n);
-  return status();
+  return launch_status();
 }
 
 }  // extern "C"

@@ -6,16 +6,12 @@
 // order (for fp32 that order is the torch_scatter / scatter_add_ order of the reference), so
 // results are bitwise reproducible run to run.
 #include "common.hpp"
+#include "host.hpp"
 #include "aerognn.h"
 
 using namespace agn;
 
 namespace {
-
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
 
 // ------------------------------------------------------------------ grouped row reductions
 // 8 contiguous elements of a row as floats (16 B of bf16, 2 x 16 B of fp32), masked at k.
@@ -868,8 +864,7 @@ int agn_segment_max(int rows, int k, int dtype, const int32_t* ptr, const int32_
                        (double*)out, out_ld, argmax);
   else
     return AGN_E_DTYPE;
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 int agn_segment_max_backward(int rows, int k, int dtype, const int32_t* argmax, const void* gout, int gout_ld,
@@ -893,8 +888,7 @@ int agn_segment_max_backward(int rows, int k, int dtype, const int32_t* argmax, 
                        gout_ld, (double*)dx, dx_ld);
   else
     return AGN_E_DTYPE;
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 int agn_gather_rows(int rows, int k, int dtype, const int32_t* idx, const void* src, int src_ld,

@@ -12,7 +12,7 @@
 // Activations never leave registers between layers (see common.hpp for the layout); only
 // the block output (and, when training, the per-layer activations) are written to HBM.
 // Each layer's packed weights are staged in LDS once per 128-row block.
-#include "common.hpp"
+#include "tile32.hpp"
 #include "aerognn.h"
 
 using namespace agn;
@@ -653,26 +653,6 @@ constexpr bool kStageGradOut = false;
 template <typename T, int NT>
 constexpr int res_layer_units() { return NT * (nrk(32 * NT) / BOp<T, 16>::RPU) * 64; }
 
-// XCD-aware tile walk: blocks b and b + 8 share an XCD (and its 4 MB L2), so each group of
-// blocks {g, g+8, ...} walks one contiguous eighth of the tiles. Consecutive CSC edge tiles
-// share receivers and nearby senders: their P_s/P_d rows are re-read from the same L2.
-struct ResTiles {
-  int first, end, step;
-  AGN_DEV ResTiles(int ntiles, int wid) {
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-      const int g = blockIdx.x & 7, bi = blockIdx.x >> 3, nb = gridDim.x >> 3;
-      const int per = (ntiles + 7) / 8;
-      first = g * per + bi * RES_WPB + wid;
-      end = min(ntiles, (g + 1) * per);
-      step = nb * RES_WPB;
-    } else {
-      first = blockIdx.x * RES_WPB + wid;
-      end = ntiles;
-      step = gridDim.x * RES_WPB;
-    }
-  }
-};
-
 // Diagnostic phase clocks of the resident edge forward (built with -DAGN_FWD_STAMPS into the
 // separate stamps library only): the 8 waves of block 0 record s_memtime at 10 points of their
 // first 8 tiles into agn_fwd_stamps[(wave * 8 + tile) * 16 + point].
@@ -709,7 +689,7 @@ __global__ __launch_bounds__(RES_BLOCK, 2) void mlp_fwd_res_kernel(const agn_mlp
   const int lane0 = threadIdx.x & 63;
   const int ntiles = (a.rows + 31) / 32;
   const agn_seg& sg = a.seg[0];
-  const ResTiles tw(ntiles, threadIdx.x >> 6);
+  const t32::Walk tw(ntiles, threadIdx.x >> 6, RES_WPB);
   // The sender / receiver ids of the wave's next tile are loaded one tile ahead, so a tile's
   // projection-row gathers issue together with its e loads (one memory latency per tile, not two).
   // They reach the next tile through the wave's LDS slot, not a loop-carried register: a
@@ -944,7 +924,7 @@ __global__ __launch_bounds__(RES_BLOCK, 2) void mlp_bwd_res_kernel(const agn_mlp
   float pg[NP], pb[NP];
 #pragma unroll
   for (int i = 0; i < NP; ++i) { pg[i] = 0.f; pb[i] = 0.f; }
-  const ResTiles tw(ntiles, wid);
+  const t32::Walk tw(ntiles, wid, RES_WPB);
   for (int tile = tw.first; tile < tw.end; tile += tw.step) {
     cbarrier();
     const int row = tile * 32 + c;
@@ -1175,11 +1155,6 @@ __global__ void reduce_partials_kernel(const float* __restrict__ p, int nw, int 
   out[cidx] = s;
 }
 
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 }  // namespace
 
 #define AGN_LAUNCH(KERNEL, T, NT, MODE)                                                              \
@@ -1226,24 +1201,26 @@ inline int launch_status() {
     }                                                                         \
   } while (0)
 
-namespace {
-int g_cus = 0;
-int num_cus() {
-  if (g_cus == 0) {
+namespace agn {
+int cu_count() {  // host.hpp
+  static int cus = 0;
+  if (cus == 0) {
     int dev = 0;
     hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) g_cus = p.multiProcessorCount;
-    if (g_cus <= 0) g_cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
+    if (cus <= 0) cus = 256;
   }
-  return g_cus;
+  return cus;
 }
+}  // namespace agn
+
+namespace {
 int res_blocks(int rows) {
   const int tiles = (rows + 31) / 32;
   const int need = (tiles + RES_WPB - 1) / RES_WPB;
-  const int cap = num_cus();  // 128 KB of resident weights: one block per CU
+  const int cap = cu_count();  // 128 KB of resident weights: one block per CU
   return need < cap ? (need > 0 ? need : 1) : cap;
 }
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 bool fwd_ptrs_aligned(const agn_mlp_fwd_args* a) {
   bool ok = al16(a->out) && al16(a->resid) && al16(a->proj) && al16(a->hpre);
   for (int s = 0; s < a->nseg; ++s) ok = ok && al16(a->seg[s].ptr) && al16(a->seg[s].store);

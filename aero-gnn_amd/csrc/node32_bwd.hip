@@ -11,19 +11,16 @@
 // 128-row block. Here W0^T (256 x 128), W3^T and W2^T stay resident (128 KB; W1^T streams from
 // L2) and 8 waves per CU stream 32-row tiles. The LayerNorm partials of a tile go to a workspace
 // and a second launch sums each 128-row block's four tiles in the general kernel's order.
-#include "common.hpp"
+#include "tile32.hpp"
 #include "aerognn.h"
 
 using namespace agn;
+using namespace agn::t32;
 
 namespace {
 
-constexpr int H = 128;
-constexpr int NT = 4;
-constexpr int NR = 64;
 constexpr int NP = NR / 32;
-constexpr int NU = 8;
-constexpr int LW = NT * NU * 64;       // a 128 x 128 image (units)
+constexpr int LW = LAYER_UNITS;        // a 128 x 128 image (units)
 constexpr int NW = 8;
 constexpr int PF = 2;
 constexpr int PFG = 4;
@@ -37,48 +34,14 @@ struct Smem {
 };
 static_assert(sizeof(Smem) <= 160 * 1024, "LDS budget");
 
-// acc[ot] += A[ot0 + ot, k-steps 0..7] . b (ot0 in output tiles of the image), k-steps in order
+// acc[ot] += A[ot0 + ot, k-steps 0..7] . b (ot0 in output tiles of the image), k-steps in order:
+// a resident image, and W1^T from L2 (tile32.hpp gemm_stream)
 AGN_DEV void gemm_l(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* w, int ot0, int lane) {
-  uint4 f[PF];
-#pragma unroll
-  for (int i = 0; i < PF; ++i) f[i] = w[((ot0 + i % NT) * NU + i / NT) * 64 + lane];
-#pragma unroll
-  for (int idx = 0; idx < NT * NU; ++idx) {
-    const uint4 cur = f[idx % PF];
-    const int nx = idx + PF;
-    if (nx < NT * NU) f[idx % PF] = w[((ot0 + nx % NT) * NU + nx / NT) * 64 + lane];
-    b.mfma(acc[idx % NT], cur, idx / NT);
-  }
+  gemm_stream<PF>(acc, b, w, NU, ot0, 0, lane);
 }
 AGN_DEV void gemm_g(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* w, int lane) {
-  uint4 f[PFG];
-#pragma unroll
-  for (int i = 0; i < PFG; ++i) f[i] = w[((i % NT) * NU + i / NT) * 64 + lane];
-#pragma unroll
-  for (int idx = 0; idx < NT * NU; ++idx) {
-    const uint4 cur = f[idx % PFG];
-    const int nx = idx + PFG;
-    if (nx < NT * NU) f[idx % PFG] = w[((nx % NT) * NU + nx / NT) * 64 + lane];
-    b.mfma(acc[idx % NT], cur, idx / NT);
-  }
+  gemm_stream<PFG>(acc, b, w, NU, 0, 0, lane);
 }
-
-struct Walk {
-  int first, end, step;
-  AGN_DEV Walk(int ntiles, int w) {
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-      const int g = blockIdx.x & 7, bi = blockIdx.x >> 3, nb = gridDim.x >> 3;
-      const int per = (ntiles + 7) / 8;
-      first = g * per + bi * NW + w;
-      end = min(ntiles, (g + 1) * per);
-      step = nb * NW;
-    } else {
-      first = blockIdx.x * NW + w;
-      end = ntiles;
-      step = gridDim.x * NW;
-    }
-  }
-};
 
 // the general kernel's load_grad (M_VEC, no g2): the row of g, zero for rows past the end
 AGN_DEV void load_g(float (&A)[NR], const bf16* g, int rr, bool valid, int h) {
@@ -107,7 +70,7 @@ __global__ __launch_bounds__(64 * NW) void node32_bwd_kernel(const agn_mlp_bwd_a
   const int lane0 = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntiles = (a.rows + 31) / 32;
-  const Walk walk(ntiles, w);
+  const Walk walk(ntiles, w, NW);
   const bf16* G = reinterpret_cast<const bf16*>(a.g);
   const bf16* HP = reinterpret_cast<const bf16*>(a.hpre);
   const uint4* w1g = reinterpret_cast<const uint4*>(a.wtpk[1]);
@@ -283,7 +246,7 @@ __global__ __launch_bounds__(64 * NW) void dec32_bwd_kernel(const agn_mlp_bwd_ar
   const int lane0 = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntiles = (a.rows + 31) / 32;
-  const Walk walk(ntiles, w);
+  const Walk walk(ntiles, w, NW);
   const bf16* G = reinterpret_cast<const bf16*>(a.g);
   // a tile's loads (the narrow g row, every layer's ReLU mask bits) are issued one tile ahead,
   // before the current tile's stores: vmcnt retires in order, so a load issued after a tile's
@@ -371,19 +334,6 @@ __global__ __launch_bounds__(64 * NW) void dec32_bwd_kernel(const agn_mlp_bwd_ar
   }
 }
 
-int g_cus = 0;
-int cu_count() {
-  if (g_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) g_cus = pr.multiProcessorCount;
-    if (g_cus <= 0) g_cus = 256;
-  }
-  return g_cus;
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // per-tile LayerNorm partial workspace, grown on demand (device memory kept for the process)
 // LayerNorm partial-row workspace, one per device (a process driving two devices must not
 // share it); a call on another stream than the last user first waits for that stream, which may still
@@ -397,11 +347,7 @@ LnScratch g_lnt[64];
 long g_launches = 0;
 long g_dec_launches = 0;
 
-int grid_for(int ntiles) {
-  const int need_blocks = (ntiles + NW - 1) / NW;
-  const int cus = cu_count();
-  return need_blocks >= cus ? cus : ((need_blocks + 7) / 8 * 8 < 8 ? 8 : (need_blocks + 7) / 8 * 8);
-}
+int grid_for(int ntiles) { return tile_blocks(ntiles, NW); }
 
 }  // namespace
 
@@ -457,8 +403,7 @@ bool node32_bwd_try(const agn_mlp_bwd_args* a, void* stream, int* rc, int* ln_ro
                        a->ln_partial);
   ++g_launches;
   *ln_rows = nblk;
-  const hipError_t e = hipGetLastError();
-  *rc = e == hipSuccess ? 0 : (int)e;
+  *rc = launch_status();
   return true;
 }
 
@@ -479,8 +424,7 @@ bool dec32_bwd_try(const agn_mlp_bwd_args* a, void* stream, int* rc) {
   if (a->nlin == 4) hipLaunchKernelGGL(dec32_bwd_kernel<4>, dim3(grid_for(ntiles)), dim3(64 * NW), 0, st, *a);
   else hipLaunchKernelGGL(dec32_bwd_kernel<3>, dim3(grid_for(ntiles)), dim3(64 * NW), 0, st, *a);
   ++g_dec_launches;
-  const hipError_t e = hipGetLastError();
-  *rc = e == hipSuccess ? 0 : (int)e;
+  *rc = launch_status();
   return true;
 }
 }  // namespace agn

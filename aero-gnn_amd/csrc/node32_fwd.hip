@@ -16,19 +16,16 @@
 // sums reach the operand layout through a 2-KB LDS buffer, then the chain runs on the MFMA as
 // edge32_fwd.hip's does. C3 level-0 node MLP: 378 against 453 us per launch for the per-lane walk at
 // 12 waves (profiles/r5_node32_walk_ab.txt), 490 us for the general kernel.
-#include "common.hpp"
+#include "tile32.hpp"
 #include "aerognn.h"
 
 using namespace agn;
+using namespace agn::t32;
 
 namespace {
 
-constexpr int H = 128;
-constexpr int NT = 4;
-constexpr int NR = 64;
-constexpr int NU = 8;                     // k-steps of 16 per 128 input features
-constexpr int L0 = NT * 2 * NU * 64;      // W0 units (K = 256)
-constexpr int L1 = NT * NU * 64;          // W1 / W2 units
+constexpr int L0 = 2 * LAYER_UNITS;       // W0 units (K = 256)
+constexpr int L1 = LAYER_UNITS;           // W1 / W2 units
 #ifndef AGN_N32_NW
 #define AGN_N32_NW 8
 #endif
@@ -51,51 +48,8 @@ template <int NLIN> struct Smem {
 };
 static_assert(sizeof(Smem<4>) <= 160 * 1024, "LDS budget");
 
-// acc[ot] += W[ot tile, units u0 .. u0+7] . b, k-steps in order (common.hpp gemm's per-accumulator
-// sequence); fragments stream PF deep, ot inner
-AGN_DEV void gemm_k8(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* w, int ku_total, int u0, int lane) {
-  uint4 f[PF];
-#pragma unroll
-  for (int i = 0; i < PF; ++i) f[i] = w[((i % NT) * ku_total + u0 + i / NT) * 64 + lane];
-#pragma unroll
-  for (int idx = 0; idx < NT * NU; ++idx) {
-    const uint4 cur = f[idx % PF];
-    const int nx = idx + PF;
-    if (nx < NT * NU) f[idx % PF] = w[((nx % NT) * ku_total + u0 + nx / NT) * 64 + lane];
-    b.mfma(acc[idx % NT], cur, idx / NT);
-  }
-}
-
-// the same from global memory (an L2-resident 32 KB image), PFG fragments in flight
-AGN_DEV void gemm_k8_g(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* w, int lane) {
-  uint4 f[PFG];
-#pragma unroll
-  for (int i = 0; i < PFG; ++i) f[i] = w[((i % NT) * NU + i / NT) * 64 + lane];
-#pragma unroll
-  for (int idx = 0; idx < NT * NU; ++idx) {
-    const uint4 cur = f[idx % PFG];
-    const int nx = idx + PFG;
-    if (nx < NT * NU) f[idx % PFG] = w[((nx % NT) * NU + nx / NT) * 64 + lane];
-    b.mfma(acc[idx % NT], cur, idx / NT);
-  }
-}
-
-struct Walk {
-  int first, end, step;
-  AGN_DEV Walk(int ntiles, int w) {
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-      const int g = blockIdx.x & 7, bi = blockIdx.x >> 3, nb = gridDim.x >> 3;
-      const int per = (ntiles + 7) / 8;
-      first = g * per + bi * NW + w;
-      end = min(ntiles, (g + 1) * per);
-      step = nb * NW;
-    } else {
-      first = blockIdx.x * NW + w;
-      end = ntiles;
-      step = gridDim.x * NW;
-    }
-  }
-};
+// The bias loops, the LayerNorm statistics and the save blocks of this kernel stay written out:
+// behind shared helpers (tile32.hpp acc_bias and the like) its instruction streams change.
 
 // SAVES: the training saves of agn_mlp_fwd_args (relu outputs act[0..1] with their AGN_RELU_MASK
 // bits, hpre, stats; row-major or AGN_TILED as a.tiled says), as the general kernel writes them
@@ -122,7 +76,7 @@ __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_a
   const int lane0 = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntiles = (a.rows + 31) / 32;
-  const Walk walk(ntiles, w);
+  const Walk walk(ntiles, w, NW);
   int* wrp = sm.rp[w];
   const agn_seg& sx = a.seg[0];
   const agn_seg& sg = a.seg[1];
@@ -249,8 +203,8 @@ __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_a
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[q / 4][4 * (q % 4) + e] = v[e];
     }
-    gemm_k8(acc, bx, sm.w0, 2 * NU, 0, lane_b);
-    gemm_k8(acc, bagg, sm.w0, 2 * NU, NU, lane_b);
+    gemm_stream<PF>(acc, bx, sm.w0, 2 * NU, 0, 0, lane_b);
+    gemm_stream<PF>(acc, bagg, sm.w0, 2 * NU, 0, NU, lane_b);
     BOp<bf16, NR> b;
 #pragma unroll
     for (int l = 1; l < NLIN; ++l) {
@@ -274,8 +228,8 @@ __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_a
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[q / 4][4 * (q % 4) + e] = v[e];
       }
-      if (l == 3) gemm_k8_g(acc, b, reinterpret_cast<const uint4*>(a.wpk[3]), lane_b);
-      else gemm_k8(acc, b, l == 1 ? sm.w1 : sm.w2, NU, 0, lane_b);
+      if (l == 3) gemm_stream<PFG>(acc, b, reinterpret_cast<const uint4*>(a.wpk[3]), NU, 0, 0, lane_b);
+      else gemm_stream<PF>(acc, b, l == 1 ? sm.w1 : sm.w2, NU, 0, 0, lane_b);
       if constexpr (SAVES) {
         if (l == 3) save();
       }
@@ -314,21 +268,8 @@ __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_a
 #pragma unroll
     for (int i = 0; i < NR / 8; ++i) {
       float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = acc[(8 * i + e) / 16][(8 * i + e) % 16];
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        const int f0 = 16 * i + 8 * jj + 4 * hb;
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(&sm.pv[NLIN][f0]);
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(&sm.pv[NLIN + 1][f0]);
-#pragma unroll
-        for (int e = 0; e < 4; e += 2) {
-          const f32x2 o = ln_out2(f2(v[4 * jj + e], v[4 * jj + e + 1]), mean, rstd, f2(g4[e], g4[e + 1]),
-                                  f2(b4[e], b4[e + 1]));
-          v[4 * jj + e] = o[0];
-          v[4 * jj + e + 1] = o[1];
-        }
-      }
+      acc_get8(v, acc, i);
+      ln_out8(v, sm.pv[NLIN], sm.pv[NLIN + 1], i, hb, mean, rstd);
       float r[8];
       bx.get8(r, i);
 #pragma unroll
@@ -342,19 +283,6 @@ __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_a
     }
   }
 }
-
-int g_cus = 0;
-int cu_count() {
-  if (g_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) g_cus = pr.multiProcessorCount;
-    if (g_cus <= 0) g_cus = 256;
-  }
-  return g_cus;
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 long g_launches = 0;  // launches so far (agn_debug_node32_launches: tests check the dispatch)
 
@@ -385,11 +313,7 @@ bool node32_fwd_try(const agn_mlp_fwd_args* a, void* stream, int* rc) {
   for (int l = 0; l < a->nlin; ++l)
     if (!a->wpk[l] || !al16(a->wpk[l])) return false;
   if (!al16(sx.ptr) || !al16(sg.ptr) || !al16(a->out) || !al16(sg.store)) return false;
-  const int tiles = (a->rows + 31) / 32;
-  const int need = (tiles + NW - 1) / NW;
-  const int cus = cu_count();
-  const int nblk = need >= cus ? cus : ((need + 7) / 8 * 8 < 8 ? 8 : (need + 7) / 8 * 8);
-  const dim3 g(nblk), blk(64 * NW);
+  const dim3 g(tile_blocks((a->rows + 31) / 32, NW)), blk(64 * NW);
   hipStream_t st = (hipStream_t)stream;
   if (a->nlin == 4) {
     if (saves) hipLaunchKernelGGL((node32_fwd_kernel<4, true>), g, blk, 0, st, *a);
@@ -399,8 +323,7 @@ bool node32_fwd_try(const agn_mlp_fwd_args* a, void* stream, int* rc) {
     else hipLaunchKernelGGL((node32_fwd_kernel<3, false>), g, blk, 0, st, *a);
   }
   ++g_launches;
-  const hipError_t e = hipGetLastError();
-  *rc = e == hipSuccess ? 0 : (int)e;
+  *rc = launch_status();
   return true;
 }
 }  // namespace agn

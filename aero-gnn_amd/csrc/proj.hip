@@ -9,37 +9,17 @@
 // staging area (1-KB contiguous instructions, common.hpp tile_load_chunks / tile_store_chunks).
 // Arithmetic, MFMA k-order and rounding are those of mlp_fwd_kernel (nlin = 1, M_VEC): outputs
 // are bitwise identical (tests/test_gpu_fullsize.py::test_proj_kernels_bitwise_equal_general).
-#include "common.hpp"
+#include "tile32.hpp"
 #include "aerognn.h"
 
 using namespace agn;
+using namespace agn::t32;
 
 namespace {
 
-constexpr int H = 128;
-constexpr int NT = 4, NR = 64;
 constexpr int PJ_WPB = 4;  // 4-wave blocks, two per CU (64 KB weights + 9 KB staging each)
 constexpr int PJ_BLOCK = 64 * PJ_WPB;
 constexpr int PJ_UNITS = 8 * 8 * 64;  // packed [8 out tiles][8 k-units] or [4][16] x 16 B: 64 KB
-
-// XCD-grouped tile walk (blocks b and b + 8 share an XCD and its L2), as the resident kernels
-struct Tiles {
-  int first, end, step;
-  AGN_DEV Tiles(int ntiles, int wid) {
-    if (gridDim.x >= 8 && (gridDim.x & 7) == 0) {
-      const int g = blockIdx.x & 7, bi = blockIdx.x >> 3, nb = gridDim.x >> 3;
-      const int per = (ntiles + 7) / 8;
-      first = g * per + bi * PJ_WPB + wid;
-      end = min(ntiles, (g + 1) * per);
-      step = nb * PJ_WPB;
-    } else {
-      first = blockIdx.x * PJ_WPB + wid;
-      end = ntiles;
-      step = gridDim.x * PJ_WPB;
-    }
-  }
-};
-
 
 // NSEG input segments of 128 features; NGRP output groups of 128 (packed matrix: NGRP * 4 out
 // tiles x NSEG * 8 k-units, unit = (ot * KU + ku) * 64 + lane)
@@ -59,7 +39,7 @@ __global__ __launch_bounds__(PJ_BLOCK, 2) void proj_kernel(int rows, const bf16*
   const int c = lane & 31, h = lane >> 5;
   const int ntiles = (rows + 31) / 32;
   const int wid = threadIdx.x >> 6;
-  const Tiles tw(ntiles, wid);
+  const Walk tw(ntiles, wid, PJ_WPB);
   for (int tile = tw.first; tile < tw.end; tile += tw.step) {
     cbarrier();  // keep the LDS weight reads inside the loop
     // one input segment (the forward's x): its tile is loaded once for both output groups, so
@@ -122,22 +102,10 @@ __global__ __launch_bounds__(PJ_BLOCK, 2) void proj_kernel(int rows, const bf16*
   }
 }
 
-int g_cus = 0;
 int blocks(int rows) {
-  if (g_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) g_cus = p.multiProcessorCount;
-    if (g_cus <= 0) g_cus = 256;
-  }
   const int need = ((rows + 31) / 32 + PJ_WPB - 1) / PJ_WPB;
-  const int cap = 2 * g_cus;  // 64 KB of LDS and 128 VGPRs: two blocks per CU
+  const int cap = 2 * cu_count();  // 64 KB of LDS and 128 VGPRs: two blocks per CU
   return need < cap ? (need > 0 ? need : 1) : cap;
-}
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-inline int status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
 }
 
 }  // namespace
@@ -153,7 +121,7 @@ int agn_proj_forward(int rows, const void* x, int x_ld, const void* wpk, const f
   hipLaunchKernelGGL((proj_kernel<1, 2>), dim3(blocks(rows)), dim3(PJ_BLOCK), 0, (hipStream_t)stream, rows,
                      (const bf16*)x, (const bf16*)nullptr, x_ld, (const uint4*)wpk, bias, (const bf16*)nullptr,
                      (bf16*)out, out_ld);
-  return status();
+  return launch_status();
 }
 
 int agn_proj_backward(int rows, const void* dps, const void* dpd, int dp_ld, const void* wtpk, void* dx, int dx_ld,
@@ -165,7 +133,7 @@ int agn_proj_backward(int rows, const void* dps, const void* dpd, int dp_ld, con
   hipLaunchKernelGGL((proj_kernel<2, 1>), dim3(blocks(rows)), dim3(PJ_BLOCK), 0, (hipStream_t)stream, rows,
                      (const bf16*)dps, (const bf16*)dpd, dp_ld, (const uint4*)wtpk, (const float*)nullptr,
                      (const bf16*)dx, (bf16*)dx, dx_ld);
-  return status();
+  return launch_status();
 }
 
 }  // extern "C"

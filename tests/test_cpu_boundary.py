@@ -155,3 +155,19 @@ def test_pack_rejects_float64_and_mixed_dtypes():
         p.update(torch.float64, torch.device("cpu"))
     with pytest.raises(TypeError):
         p.update(torch.float32, torch.device("cpu"))
+
+
+def test_tile_block_counts():
+    """The block-count rule the persistent tile kernels share (csrc/host.hpp tile_blocks), through
+    the two exports that expose it: every CU once there is work for all, else the blocks needed
+    rounded up to a multiple of 8, at least 8. The values hold for any device with >= 32 CUs
+    (256 is assumed without one)."""
+    from aerognn import _lib
+    lib = _lib.lib()
+    table = {0: (8, 8), 1: (8, 8), 17: (8, 8), 1025: (8, 16), 3072: (8, 24), 3073: (16, 32)}
+    for rows, want in table.items():
+        assert (lib.agn_edge_fwd32_blocks(rows), lib.agn_edge_bwd_blocks(rows)) == want, rows
+    for fn in (lib.agn_edge_fwd32_blocks, lib.agn_edge_bwd_blocks):
+        counts = [fn(rows) for rows in list(range(0, 4100)) + list(range(4100, 400000, 997))]
+        assert all(n % 8 == 0 for n in counts)
+        assert all(a <= b for a, b in zip(counts, counts[1:]))
