@@ -122,7 +122,7 @@ _lib = None
 # of them is bracketed by HIP events on the caller's current stream (the stream the launch goes
 # to) and recorded under its name, unless an enclosing core.timed(...) already times it under a
 # finer tag (edge_fwd, node_bwd, ...). Nothing is recorded when PROF is None.
-LAUNCHES = ("agn_pack", "agn_mlp_forward", "agn_mlp_backward", "agn_reduce_partials", "agn_wgrad", "agn_colsum",
+LAUNCHES = ("agn_pack", "agn_mlp_forward", "agn_mlp_backward", "agn_reduce_partials", "agn_wgrad", "agn_wgrad_segsum", "agn_colsum",
             "agn_segment_sum", "agn_segment_sum2", "agn_gather_rows", "agn_radix_sort_u64", "agn_row_ptr", "agn_row_ptr_i64",
             "agn_iota_keys", "agn_level_index",
             "agn_exclusive_scan_i32", "agn_pool_sort_keys", "agn_pool_assign", "agn_pool_edge_candidates",
@@ -192,6 +192,8 @@ def lib():
             "agn_wgrad_partial_floats": (C.c_size_t, [i32, i32, i32]),
             "agn_wgrad": (i32, [C.POINTER(WgradBatch), i32, i32, vp]),
             "agn_wgrad_plan": (i32, [C.POINTER(WgradBatch)]),
+            "agn_wgrad_segsum": (i32, [C.POINTER(WgradBatch), i32, i32, vp, vp, i32, vp, i32, vp]),
+            "agn_debug_wgrad_occupancy": (i32, [i32]),
             "agn_colsum": (i32, [vp, i32, i32, vp, i32, vp, vp]),
             "agn_segment_sum": (i32, [i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]),
             "agn_segment_sum2": (i32, [i32, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp]),

@@ -664,6 +664,43 @@ class WGrad:
         self.items = []
 
 
+# dW_e and the receiver sums dP_d of the sum-trick edge block in one pass over G0
+# (agn_wgrad_segsum); bitwise the segment_sum + WGrad launches that AEROGNN_WG_DPD=0 selects.
+def wgrad_dpd_ok(g, x):
+    import os
+    return (os.environ.get("AEROGNN_WG_DPD", "1") != "0" and g.dtype in (torch.bfloat16, torch.float16)
+            and g.dtype == x.dtype and g.dim() == 2 and x.dim() == 2 and g.shape[1] == 128 and x.shape[1] == 128
+            and g.stride(1) == 1 and x.stride(1) == 1 and not is_tiled(g) and not is_tiled(x))
+
+
+def wgrad_segsum(G, X, dw, rowptr, dst, out, tag="wgrad_edge"):
+    """dw = G^T X (fp32 [128][>=128] view) and out[n] = sum of G's rows rowptr[n]..rowptr[n+1]-1
+    ([N, 128] of G's dtype; dst[r] = the receiver n of row r), with the split plan of a one-desc
+    WGrad.run()."""
+    lib = L.lib()
+    rows, N = G.shape[0], out.shape[0]
+    assert X.shape[0] == rows and rowptr.dtype == torch.int32 and rowptr.numel() == N + 1
+    assert dst.dtype == torch.int32 and dst.numel() == rows and dst.is_contiguous() and rowptr.is_contiguous()
+    assert dw.dtype == torch.float32 and dw.stride(1) == 1 and out.dtype == G.dtype and out.stride(1) == 1
+    b = L.WgradBatch()
+    b.n = 1
+    b.d[0] = L.WgradDesc(ptr(G), ptr(X), G.stride(0), X.stride(0), 128, 128, rows, dw.stride(0), None, None, ptr(dw),
+                         None, 0, 0, 0, 0, None)
+    scratch = None
+    if rows > 0:
+        check(lib.agn_wgrad_plan(C.byref(b)), "wgrad_plan")
+        scratch = torch.empty(int(lib.agn_wgrad_partial_floats(128, 128, b.d[0].nsplit)), dtype=torch.float32,
+                              device=G.device)
+        b.d[0].dw_partial = ptr(scratch)
+    # WGrad.run's operator I/O plus the [N,128] sums written and the index read
+    s_el = G.element_size()
+    io = rows * 256 * s_el + 4 * 128 * 129 + N * 128 * s_el + 4 * (N + 1)
+    with timed(tag, (0.0, 2.0 * rows * 128 * 128, io)):
+        check(lib.agn_wgrad_segsum(C.byref(b), dt_code(G.dtype), 0, ptr(rowptr), ptr(dst), N, ptr(out), out.stride(0), stream()),
+              "wgrad_segsum")
+    return out
+
+
 # --------------------------------------------------------------------------- algorithmic costs
 # Each tagged launch records (alg_bytes, flops, impl_bytes):
 #   alg_bytes  = the launch's share of SURVEY §8(d)'s fully-fused per-layer minimum

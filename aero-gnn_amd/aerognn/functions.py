@@ -25,7 +25,7 @@ from . import core as _core
 from .core import (Pack, WGrad, alg8d_edge, alg8d_node, with_alg, edge_bwd_fused, fused_edge_train_ok, bwd_nblocks,
                    edge32_ok, edge_saves_ok, edge_forward,
                    cost_edge_bwd_fused,
-                   proj_kernel_ok, proj_forward, proj_backward, tiled_empty, relu_mask_empty, colsum_rows, cost_edge_bwd, cost_edge_bwd_cat, cost_edge_fwd,
+                   proj_kernel_ok, proj_forward, proj_backward, wgrad_dpd_ok, wgrad_segsum, tiled_empty, relu_mask_empty, colsum_rows, cost_edge_bwd, cost_edge_bwd_cat, cost_edge_fwd,
                    cost_edge_fwd_cat, cost_node_bwd, cost_node_fwd, cost_proj, cost_wec_bwd, cost_wec_fwd, dt_code,
                    timed, gather_rows, mlp_backward, mlp_forward, require_device,
                    scatter_rows, segment_max, segment_max_backward, segment_sum, segment_sum2, stream)
@@ -556,7 +556,15 @@ class GMPFn(torch.autograd.Function):
             # (dP_d formed on the fused kernel's dW waves, round 5, measured slower once the chain
             # waves got faster: DESIGN.md §9 round 6)
             dPs = segment_sum(N, H, lv.rowptr_src, lv.perm_src, g0, torch.empty(N, H, dtype=dt, device=dev))
-            dPd = segment_sum(N, H, lv.rowptr, None, g0, torch.empty(N, H, dtype=dt, device=dev))
+            dPd = torch.empty(N, H, dtype=dt, device=dev)
+            # dP_d and dW_e = G0^T e walk G0's rows in the same (CSC) order: one pass forms both,
+            # bitwise the two launches it replaces ("dP_d inside the dW_e pass")
+            dwe = None
+            if fused and wgrad_dpd_ok(g0, e):
+                dwe = torch.empty(H, H, dtype=torch.float32, device=dev)
+                wgrad_segsum(g0, e, dwe, lv.rowptr, lv.dst, dPd)
+            else:
+                segment_sum(N, H, lv.rowptr, None, g0, dPd)
             if proj_kernel_ok(dx, H):
                 s_el = dx.element_size()
                 proj_backward(N, dPs, dPd, spec.pack["projT"], dx, tag="proj_bwd",
@@ -571,10 +579,11 @@ class GMPFn(torch.autograd.Function):
             # different row counts leaves most workgroups idle behind the edge descs (measured)
             wg = WGrad("wgrad_node")
             if fused:
-                dwe = torch.empty(H, H, dtype=torch.float32, device=dev)
-                we = WGrad("wgrad_edge")
-                we.add(g0, e, dwe)
-                we.run()
+                if dwe is None:
+                    dwe = torch.empty(H, H, dtype=torch.float32, device=dev)
+                    we = WGrad("wgrad_edge")
+                    we.add(g0, e, dwe)
+                    we.run()
                 eg = [dwe]
                 for l in range(3):
                     eg += [dW13[l], db13[l]]

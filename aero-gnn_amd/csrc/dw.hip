@@ -160,10 +160,120 @@ AGN_DEV bf16x8 tr_frag(const bf16* lds, int kb, int col_base, int lane) {
   return r;
 }
 
+// The receiver sums of agn_wgrad_segsum: out[n] = sum of G's rows ptr[n]..ptr[n+1]-1 (CSC order)
+struct WgSeg {
+  const int32_t* ptr;  // [n + 1]
+  const int32_t* dst;  // [rows]: the receiver of each row
+  int n;
+  void* out;           // T [n][out_ld]
+  int out_ld;
+};
+
+// One wave's walk over its receivers. Everything but the two sums is wave-uniform; the index is
+// read through the constant address space (nothing writes it while the kernel runs), so its loads
+// are scalar loads that do not queue behind the stage prefetch. Every index value is clamped to
+// [0, rows], so a malformed index bounds every loop and keeps every read inside G.
+template <typename T>
+struct SegWalk {
+  typedef const __attribute__((address_space(4))) int32_t* cptr_t;
+  cptr_t ptr, dst;
+  int rows;           // rows of G
+  int n, nhi;         // this wave's current receiver, end of the split's receivers
+  int cur, end;       // next row to add and end of receiver n's range (when open)
+  bool open;
+  float s0, s1;
+
+  AGN_DEV int at(int i) const { return min(max(ptr[i], 0), rows); }
+  // first receiver n with at(n) >= r, for a row r < rows: found from r's own receiver (a search of
+  // the index costs ~20 dependent loads before the first stage; this costs two or three)
+  AGN_DEV int first_from(int cnt, int r) const {
+    int i = min(max(dst[r], 0), cnt - 1);
+    if (at(i) < r) return i + 1;          // r's receiver starts before r
+    while (i > 0 && at(i - 1) >= r) --i;  // empty receivers at r
+    return i;
+  }
+  AGN_DEV void init(const WgSeg& sa, int rows_, int rbeg, int per, int wave) {
+    ptr = (cptr_t)(uintptr_t)sa.ptr;
+    dst = (cptr_t)(uintptr_t)sa.dst;
+    rows = rows_;
+    n = nhi = 0;
+    cur = end = 0;
+    open = false;
+    s0 = s1 = 0.f;
+    if (rbeg >= rows || sa.n < 1) return;  // a split without rows owns nothing
+    const int nlo = first_from(sa.n, rbeg);
+    nhi = per >= rows - rbeg ? sa.n : first_from(sa.n, rbeg + per);
+    n = nlo + ((wave - nlo) & 3);
+  }
+  AGN_DEV bool next() {
+    if (n >= nhi) return false;
+    cur = at(n);
+    end = max(cur, at(n + 1));
+    s0 = s1 = 0.f;
+    open = true;
+    return true;
+  }
+  // rows [from, stop) of a [.][ld] matrix whose row `base` is at p; 4 loads in flight, added in order
+  AGN_DEV void add_rows(const T* p, size_t ld, int base, int from, int stop, int lane) {
+    for (int r = from; r < stop; r += 4) {
+      uint32_t v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        v[q] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(p + (size_t)(min(r + q, stop - 1) - base) * ld) +
+                                                  (uint32_t)(4 * lane));
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (r + q < stop) {
+          s0 += lo16<T>(v[q]);
+          s1 += hi16<T>(v[q]);
+        }
+    }
+  }
+  AGN_DEV void finish(const WgSeg& sa, int lane) {
+    *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(reinterpret_cast<T*>(sa.out) + (size_t)n * sa.out_ld) +
+                                 (uint32_t)(4 * lane)) = pack2t<T>(s0, s1);
+    open = false;
+    n += 4;
+  }
+  // the staged rows [r0, se) (se = the stage's end within the split): every receiver of this wave
+  // that starts before se, up to se
+  AGN_DEV void stage(const WgSeg& sa, const T* sg, int ld, int r0, int se, int lane) {
+    for (;;) {
+      if (!open && !next()) break;
+      if (cur < end && cur >= se) break;
+      const int stop = min(end, se);
+      add_rows(sg, ld, r0, max(cur, r0), stop, lane);
+      cur = max(cur, stop);
+      if (cur < end) break;  // runs on into the next stage, or past the split's end
+      finish(sa, lane);
+    }
+  }
+  // after the last stage: the rest of a range that passes the split's end, from global memory, and
+  // the empty receivers left
+  AGN_DEV void drain(const WgSeg& sa, const T* G, int ldg, int lane) {
+    for (;;) {
+      if (!open && !next()) break;
+      add_rows(G, ldg, 0, cur, end, lane);
+      finish(sa, lane);
+    }
+  }
+};
+
 // grid: x = row chunk (split), y = M block * nKb + K block, z = desc
 // XG: some desc has a gathered X (xidx); a separate instantiation keeps the plain path free of it
-template <typename T, bool XG>
-__global__ __launch_bounds__(DW_THREADS) void wgrad_kernel(const agn_wgrad_batch b, int nsplit) {
+// SEG (agn_wgrad_segsum; one 16-bit row-major desc, m == k == 128): the receiver sums of G's rows
+// are formed from the staged tile as well. A receiver belongs to the split that holds its first
+// row (an empty one to the split that holds ptr[n], those at ptr[n] == rows to the last split with
+// rows), so every row of out has one writer and nothing passes between workgroups. Wave w walks
+// the receivers n == w (mod 4) of its split in ascending order, lane l columns 2l, 2l + 1: per
+// receiver and column the fp32 adds of segment_sum4_kernel (graph.hip) from 0 in edge order, one
+// rounding. The split's first receiver is found from dst (the receiver of the split's first row).
+// A sum that runs on into the next stage stays in the wave's registers; rows past the split's end
+// are read from global memory. The MFMA stream is the plain kernel's.
+// (SEG asks the compiler for 3 workgroups per CU, the plain bf16 kernel's residency that
+// agn_wgrad_nsplit plans on; the other instantiations are built as before)
+template <typename T, bool XG, bool SEG = false>
+__global__ __launch_bounds__(DW_THREADS, SEG ? 3 : 1) void wgrad_kernel(const agn_wgrad_batch b, int nsplit, const WgSeg sa) {
   constexpr int LD = DwTile<T>::LD;
   __shared__ __attribute__((aligned(16))) T sg[DW_ROWS * LD];
   __shared__ __attribute__((aligned(16))) T sx[DW_ROWS * LD];
@@ -191,10 +301,12 @@ __global__ __launch_bounds__(DW_THREADS) void wgrad_kernel(const agn_wgrad_batch
   float bsum = 0.f;
   __shared__ float bhalf[DW_BLK];
   StageRegs<T> rg, rx;
+  SegWalk<typename std::conditional<SEG, T, bf16>::type> walk;
   if (rbeg < rend) {
     rg.load(G, d.ldg, rend, d.m, rbeg, m0, d.g_tiled);
     rx.load(X, d.ldx, rend, d.k, rbeg, k0, d.x_tiled, XG ? d.xidx : nullptr);
   }
+  if constexpr (SEG) walk.init(sa, d.rows, rbeg, per, __builtin_amdgcn_readfirstlane(w));
   for (int r0 = rbeg; r0 < rend; r0 += DW_ROWS) {
     __syncthreads();
     rg.store(sg, d.g_tiled);
@@ -204,6 +316,7 @@ __global__ __launch_bounds__(DW_THREADS) void wgrad_kernel(const agn_wgrad_batch
       rg.load(G, d.ldg, rend, d.m, r0 + DW_ROWS, m0, d.g_tiled);
       rx.load(X, d.ldx, rend, d.k, r0 + DW_ROWS, k0, d.x_tiled, XG ? d.xidx : nullptr);
     }
+    if constexpr (SEG) walk.stage(sa, sg, LD, r0, min(r0 + DW_ROWS, rend), lane);
     if (d.db_partial && kb == 0) {
       const int col = threadIdx.x & (DW_BLK - 1), q = threadIdx.x >> 7;
 #pragma unroll
@@ -249,6 +362,7 @@ __global__ __launch_bounds__(DW_THREADS) void wgrad_kernel(const agn_wgrad_batch
       }
     }
   }
+  if constexpr (SEG) walk.drain(sa, G, d.ldg, lane);
   // partial slab [split][mpad][kpad] with mpad = nMb*128, kpad = nKb*128
   const int kpad = nKb * DW_BLK;
   float* P = d.dw_partial + (size_t)split * (nMb * DW_BLK) * kpad;
@@ -461,8 +575,8 @@ int agn_wgrad(const agn_wgrad_batch* b, int dtype, int nsplit, void* stream) {
   for (int i = 0; i < bb.n; ++i) xg = xg || bb.d[i].xidx != nullptr;
 #define AGN_WG(T)                                                                             \
   do {                                                                                        \
-    if (xg) hipLaunchKernelGGL((wgrad_kernel<T, true>), grid, dim3(DW_THREADS), 0, st, bb, ns); \
-    else hipLaunchKernelGGL((wgrad_kernel<T, false>), grid, dim3(DW_THREADS), 0, st, bb, ns);   \
+    if (xg) hipLaunchKernelGGL((wgrad_kernel<T, true>), grid, dim3(DW_THREADS), 0, st, bb, ns, WgSeg{}); \
+    else hipLaunchKernelGGL((wgrad_kernel<T, false>), grid, dim3(DW_THREADS), 0, st, bb, ns, WgSeg{});   \
   } while (0)
   if (dtype == AGN_BF16) AGN_WG(bf16);
   else if (dtype == AGN_F16) AGN_WG(f16);
@@ -471,6 +585,41 @@ int agn_wgrad(const agn_wgrad_batch* b, int dtype, int nsplit, void* stream) {
 #undef AGN_WG
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((maxq + RED_Q - 1) / RED_Q, bb.n), dim3(RED_Q * RED_G), 0, st, bb);
   return launch_status();
+}
+
+int agn_wgrad_segsum(const agn_wgrad_batch* b, int dtype, int nsplit, const int32_t* rowptr, const int32_t* dst, int n,
+                     void* out, int out_ld, void* stream) {
+  if (!b || b->n != 1 || n < 0 || (n > 0 && (!rowptr || !out))) return AGN_E_ARG;
+  if (dtype != AGN_BF16 && dtype != AGN_F16) return AGN_E_DTYPE;
+  agn_wgrad_batch bb = *b;
+  agn_wgrad_desc& d = bb.d[0];
+  if (d.rows < 0 || !d.dw) return AGN_E_ARG;
+  if (d.m != DW_BLK || d.k != DW_BLK || d.g_tiled || d.x_tiled || d.xidx || d.db || d.db_partial) return AGN_E_SHAPE;
+  if (out_ld < DW_BLK || (out_ld & 1) || (reinterpret_cast<uintptr_t>(out) & 3)) return AGN_E_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  if (d.rows == 0) {
+    hipError_t e = hipMemset2DAsync(d.dw, sizeof(float) * d.ldw, 0, sizeof(float) * d.k, d.m, st);
+    if (e == hipSuccess && n > 0) e = hipMemset2DAsync(out, (size_t)2 * out_ld, 0, (size_t)2 * DW_BLK, n, st);
+    return e == hipSuccess ? 0 : (int)e;
+  }
+  if (!dst || n < 1) return AGN_E_ARG;  // rows without a receiver
+  // the walk reads 4-B column pairs of G's rows from global memory past a split's end
+  if (!d.g || !d.x || !d.dw_partial || (d.ldg & 1) || (reinterpret_cast<uintptr_t>(d.g) & 3)) return AGN_E_SHAPE;
+  if (nsplit > 0) d.nsplit = nsplit;
+  if (d.nsplit < 1) return AGN_E_ARG;
+  const int ns = d.nsplit;
+  const WgSeg sa{rowptr, dst, n, out, out_ld};
+  if (dtype == AGN_BF16) hipLaunchKernelGGL((wgrad_kernel<bf16, false, true>), dim3(ns, 1, 1), dim3(DW_THREADS), 0, st, bb, ns, sa);
+  else hipLaunchKernelGGL((wgrad_kernel<f16, false, true>), dim3(ns, 1, 1), dim3(DW_THREADS), 0, st, bb, ns, sa);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((DW_BLK * DW_BLK / 4 + RED_Q - 1) / RED_Q, 1), dim3(RED_Q * RED_G), 0, st, bb);
+  return launch_status();
+}
+
+int agn_debug_wgrad_occupancy(int segsum) {
+  int per = 0;
+  const hipError_t e = segsum ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, wgrad_kernel<bf16, false, true>, DW_THREADS, 0)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, wgrad_kernel<bf16, false>, DW_THREADS, 0);
+  return e == hipSuccess ? per : 0;
 }
 
 int agn_wgrad_reduce(const agn_wgrad_batch* b, int nsplit, void* stream) {

@@ -189,6 +189,22 @@ size_t agn_wgrad_partial_floats(int m, int k, int nsplit);
 int agn_wgrad_plan(agn_wgrad_batch* b);
 /* nsplit > 0: every desc uses nsplit splits; nsplit <= 0: each desc uses its own d[i].nsplit */
 int agn_wgrad(const agn_wgrad_batch* b, int dtype, int nsplit, void* stream);
+/* The sum-trick edge block's first Linear (mgnLayer.py:97-99, h0 = e W_e^T + P_s[src] + P_d[dst]):
+ * dW_e = G0^T e and the receiver sums dP_d[n] = sum of G0's rows rowptr[n]..rowptr[n+1]-1 (CSC
+ * order) in one pass over G0; the sums are taken from the row tiles the dW pass stages on chip.
+ * b holds one desc: 16-bit row-major g and x, m == k == 128, no xidx, no db (else AGN_E_SHAPE);
+ * rowptr is int32[n + 1], dst int32[rows] the receiver of each row (rowptr[dst[r]] <= r <
+ * rowptr[dst[r] + 1]), out is [n][out_ld] of the operand dtype. Two bitwise guarantees:
+ *   dw  is what agn_wgrad(b, dtype, nsplit, .) writes (same splits, stages, MFMA order, reduce);
+ *   out is what agn_segment_sum(n, 128, dtype, rowptr, NULL, g, ldg, out, out_ld, 0, .) writes
+ *       (per receiver and column fp32 adds from 0 in ascending edge order, one rounding).
+ * A receiver is summed by the split that holds its first row, so each row of out has one writer:
+ * no atomics and nothing passed between workgroups. rows == 0: dw and out are zeroed, no launch. */
+int agn_wgrad_segsum(const agn_wgrad_batch* b, int dtype, int nsplit, const int32_t* rowptr, const int32_t* dst, int n,
+                     void* out, int out_ld, void* stream);
+/* resident workgroups per CU of the bf16 agn_wgrad kernel (segsum = 0) or of its agn_wgrad_segsum
+ * variant (1); agn_wgrad_nsplit is built on the former. 0 if the query fails. */
+int agn_debug_wgrad_occupancy(int segsum);
 /* out[c] = sum_r p[r][c] (r < nw, c < n) in fixed order via scratch[scratch_rows][n] */
 int agn_colsum(const float* p, int nw, int n, float* scratch, int scratch_rows, float* out, void* stream);
 
