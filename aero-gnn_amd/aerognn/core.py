@@ -586,6 +586,23 @@ def scatter_rows(idx32, src, out):
     return out
 
 
+def fourier_embed(x, d, freq_start, freq_len, with_input, out):
+    """out = [x | emb] (with_input) or emb of the first d columns of x [n, k] (row stride x.stride(0),
+    unit column stride): fouriermgn.py:111-151, :167-170 in one launch."""
+    check(L.lib().agn_fourier_embed(dt_code(x.dtype), x.shape[0], x.shape[1], ptr(x), x.stride(0), int(d),
+                                    int(freq_start), int(freq_len), int(with_input), ptr(out), out.stride(0),
+                                    stream()), "fourier_embed")
+    return out
+
+
+def fourier_embed_bwd(x, d, freq_start, freq_len, with_input, g, dx):
+    """dx [n, k] = the input gradient of fourier_embed for the output gradient g (trig recomputed from x)."""
+    check(L.lib().agn_fourier_embed_bwd(dt_code(x.dtype), x.shape[0], x.shape[1], ptr(x), x.stride(0), int(d),
+                                        int(freq_start), int(freq_len), int(with_input), ptr(g), g.stride(0),
+                                        ptr(dx), dx.stride(0), stream()), "fourier_embed_bwd")
+    return dx
+
+
 def colsum_rows(p, nw, n, out):
     """out[c] = sum_r p[r][c] over nw rows, deterministic 2-level reduction (LN parameter grads)."""
     sr = min(512, max(1, nw))

@@ -1,6 +1,7 @@
 """autograd.Functions over the libaerognn kernels: one per reference block.
 
   MLPFn        models/mlp.py:40-51 (encoders, decoder, any MLP)
+  FourierEmbedFn  models/fouriermgn.py:111-151, :167-170 ([x | Fourier features] of the node input)
   GMPFn        models/mgnLayer.py:177-213 (EdgeBlockSum / EdgeBlock + NodeBlock + residuals)
   PoolNodeFn   bsms_mgn.py:265-267 scatter_mean of node latents (and pos)
   PoolEdgeFn   bsms_mgn.py:283     scatter_mean of edge latents over coalesced edges
@@ -305,6 +306,48 @@ def to_csc(x, lv):
 def from_csc(x, lv):
     """Rows in the level's CSC order -> the caller's edge order (x[lv.perm_inv])."""
     return PermuteRowsFn.apply(x, lv.inv32, lv.perm32)
+
+
+# --------------------------------------------------------------------------- Fourier features
+def _rows_ld(t):
+    """A 2-D tensor the kernels can read through a row stride: unit column stride and rows that do
+    not overlap (a column slice of a wider tensor passes as it is); anything else is copied."""
+    if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]):
+        return t
+    return t.contiguous()
+
+
+def fourier_width(k, d, freq_len, with_input):
+    return (k if with_input else 0) + 2 * d * freq_len
+
+
+class FourierEmbedFn(torch.autograd.Function):
+    """fouriermgn.py:111-151 (+ the torch.cat of :167-170 when with_input): [x | emb] or emb of the
+    first d columns of x at freq_len frequencies 2^(freq_start + i) pi, one agn_fourier_embed launch.
+    Nothing but x is saved; the backward (agn_fourier_embed_bwd) recomputes the trig. x is the only
+    differentiable input, so autograd runs it only when x needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, d, freq_start, freq_len, with_input):
+        require_device(x)
+        if x.dim() != 2:
+            raise ValueError(f"fourier_embed: expected a 2-D [rows, features] tensor, got shape {tuple(x.shape)}")
+        x = _rows_ld(x)
+        with_input = bool(with_input)
+        out = torch.empty(x.shape[0], fourier_width(x.shape[1], d, freq_len, with_input), dtype=x.dtype,
+                          device=x.device)
+        _core.fourier_embed(x, d, freq_start, freq_len, with_input, out)
+        ctx.cfg = (int(d), int(freq_start), int(freq_len), with_input)
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        g = _rows_ld(g)
+        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        _core.fourier_embed_bwd(x, *ctx.cfg, g, dx)
+        return dx, None, None, None, None
 
 
 # --------------------------------------------------------------------------- GMP layer

@@ -21,6 +21,10 @@ torch.compile / FakeTensorMode, and autograd formulas that are themselves torch.
       agn_segment_max_backward (gradient to the argmax row only).
   edge_features(pos [N,d], edge_index [2,E], mean=None, std=None) -> [E, d+1]
       [pos[dst] - pos[src], |.|] (dataset.py:52-62), optionally normalised: agn_edge_features.
+  fourier_embed(x [n,k], d, freq_start, freq_len, with_input=True) -> [n, k * with_input + 2 * d * freq_len]
+      [x | cos(f_i x_j), sin(f_i x_j)] of the first d columns, f_i = 2^(freq_start + i) pi
+      (fouriermgn.py:111-151, :167-170): agn_fourier_embed. Backward: fourier_embed_backward
+      (agn_fourier_embed_bwd, the trig recomputed from x).
 
 The fused MLP / MeshGraphNet-layer kernels are not registered as operators: their calls carry
 packed-weight caches and a per-level CSC plan (Python objects), so they stay
@@ -218,6 +222,63 @@ def edge_features(pos: Tensor, edge_index: Tensor, mean: Optional[Tensor] = None
 @edge_features.register_fake
 def _(pos, edge_index, mean=None, std=None):
     return pos.new_empty(edge_index.shape[1], pos.shape[1] + 1, dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------- fourier_embed
+def _embed_rows(t: Tensor, what: str) -> Tensor:
+    from .functions import _rows_ld
+    if t.dim() != 2:
+        raise ValueError(f"{what}: expected a 2-D [rows, features] tensor, got shape {tuple(t.shape)}")
+    return _rows_ld(t)
+
+
+@torch.library.custom_op("aerognn::fourier_embed", mutates_args=())
+def fourier_embed(x: Tensor, d: int, freq_start: int, freq_len: int, with_input: bool = True) -> Tensor:
+    from .core import fourier_embed as _embed
+    from .functions import fourier_width
+    require_device(x)
+    x = _embed_rows(x, "fourier_embed")
+    out = torch.empty(x.shape[0], fourier_width(x.shape[1], d, freq_len, with_input), dtype=x.dtype, device=x.device)
+    return _embed(x, d, freq_start, freq_len, with_input, out)
+
+
+@fourier_embed.register_fake
+def _(x, d, freq_start, freq_len, with_input=True):
+    return x.new_empty(x.shape[0], (x.shape[1] if with_input else 0) + 2 * d * freq_len)
+
+
+@torch.library.custom_op("aerognn::fourier_embed_backward", mutates_args=())
+def fourier_embed_backward(grad: Tensor, x: Tensor, d: int, freq_start: int, freq_len: int,
+                           with_input: bool) -> Tensor:
+    from .core import fourier_embed_bwd as _embed_bwd
+    require_device(grad, x)
+    x = _embed_rows(x, "fourier_embed_backward")
+    grad = _embed_rows(grad, "fourier_embed_backward")
+    from .functions import fourier_width
+    # the kernel trusts the row width: a narrower grad would be read past its rows
+    if grad.dtype != x.dtype or grad.shape != (x.shape[0], fourier_width(x.shape[1], d, freq_len, with_input)):
+        raise ValueError("fourier_embed_backward: grad must have x's dtype and the forward output's shape")
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    return _embed_bwd(x, d, freq_start, freq_len, with_input, grad, dx)
+
+
+@fourier_embed_backward.register_fake
+def _(grad, x, d, freq_start, freq_len, with_input):
+    return x.new_empty(x.shape[0], x.shape[1])
+
+
+def _fourier_ctx(ctx, inputs, output):
+    x, d, freq_start, freq_len, with_input = inputs
+    ctx.save_for_backward(x)
+    ctx.cfg = (d, freq_start, freq_len, with_input)
+
+
+def _fourier_bwd(ctx, g):
+    (x,) = ctx.saved_tensors
+    return torch.ops.aerognn.fourier_embed_backward(g, x, *ctx.cfg), None, None, None, None
+
+
+torch.library.register_autograd("aerognn::fourier_embed", _fourier_bwd, setup_context=_fourier_ctx)
 
 
 # ------------------------------------------------------------------------------- PyG-style pools

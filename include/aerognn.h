@@ -505,6 +505,28 @@ int agn_col_stats(int n, int k, const float* x, int ld, float* mean, float* std,
 int agn_collate(int B, int64_t ne, int64_t nn, const int64_t* edge_off, const int64_t* node_off, int64_t* edge_index,
                 int64_t* batch, void* stream);
 
+/* ---- Fourier feature map of FourierMeshGraphNet (fouriermgn.py:111-151 fourier_embedding and the
+ * torch.cat with the node features, :167-170), one launch each way. x is [n][k] with row stride ld;
+ * the first d <= k columns are embedded at the F = freq_len frequencies f_i = 2^(freq_start + i) pi:
+ *   emb[r] = for j < d: cos(f_0 x_j) .. cos(f_{F-1} x_j), sin(f_0 x_j) .. sin(f_{F-1} x_j)
+ * with_input = 1 writes [x | emb] (k + 2 d F columns per row), 0 writes emb alone (2 d F columns).
+ * dtype AGN_F32 / AGN_F64 compute in that type, AGN_BF16 / AGN_F16 in fp32 with one rounding on store.
+ * Rounding contract: f_i is the rounded pi scaled exactly, a = f_i * x_j is rounded once on its own
+ * (no FMA), cos / sin are the accurate library functions of a.
+ * Errors: AGN_E_ARG (null pointer, n < 0), AGN_E_DTYPE, AGN_E_SHAPE (d < 1, d > k, freq_len outside
+ * 1..32, |freq_start| or |freq_start + freq_len| > 30, ld < k, out_ld / g_ld / dx_ld narrower than
+ * the row it holds). n == 0 returns 0 without a launch. */
+int agn_fourier_embed(int dtype, int n, int k, const void* x, int ld, int d, int freq_start, int freq_len,
+                      int with_input, void* out, int out_ld, void* stream);
+/* Autograd of agn_fourier_embed (fouriermgn.py:111-151 and :167-170 backward): g is the gradient of
+ * the forward's output ([n][g_ld], the same with_input), dx is [n][dx_ld] with k columns written:
+ *   j <  d: dx[r][j] = (with_input ? g[r][j] : 0) + sum_i f_i (cos(a_ij) g_sin[r][j][i] - sin(a_ij) g_cos[r][j][i])
+ *   j >= d: dx[r][j] = with_input ? g[r][j] : 0
+ * i ascending, accumulated in fp32 (fp64 for AGN_F64), one rounding; the trig is recomputed from x
+ * (the forward saves nothing). */
+int agn_fourier_embed_bwd(int dtype, int n, int k, const void* x, int ld, int d, int freq_start, int freq_len,
+                          int with_input, const void* g, int g_ld, void* dx, int dx_ld, void* stream);
+
 /* ---- float64 mode (train.py:20-40 precision "double" / "float64"): the MLP / GMP path in fp64
  * on plain LDS-tiled FMA kernels (csrc/f64.hip); graph ops take dtype AGN_F64. */
 typedef struct {
