@@ -90,7 +90,7 @@ class EdgeBwdArgs(C.Structure):
 class EdgeFwdArgs(C.Structure):
     _fields_ = [("rows", i32), ("nblk", i32), ("wpk", vp * 4), ("bias", vp * 4), ("ln_g", vp), ("ln_b", vp),
                 ("e", vp), ("proj", vp), ("src", vp), ("dst", vp), ("out", vp), ("act", vp * 3), ("hpre", vp),
-                ("stats", vp)]
+                ("stats", vp), ("agg", vp), ("rowptr", vp), ("nodes", i32), ("_pad", i32)]
 
 
 class PackDesc(C.Structure):
@@ -130,7 +130,7 @@ LAUNCHES = ("agn_pack", "agn_mlp_forward", "agn_mlp_backward", "agn_reduce_parti
             "agn_bistride_select", "agn_index_map", "agn_subgraph_edges", "agn_scatter_rows", "agn_wec_forward",
             "agn_wec_backward", "agn_edge_features", "agn_node_features", "agn_normalize", "agn_col_stats", "agn_collate",
             "agn_segment_max", "agn_segment_max_backward", "agn_edge_bwd_fused", "agn_encoder_bwd_fused", "agn_wgrad_reduce",
-            "agn_edge_forward32",
+            "agn_edge_forward32", "agn_edge_agg_fixup",
             "agn_proj_forward", "agn_proj_backward", "agn_fourier_embed", "agn_fourier_embed_bwd")
 
 
@@ -234,6 +234,8 @@ def lib():
             "agn_encoder_bwd_fused": (i32, [C.POINTER(EdgeBwdArgs), vp]),
             "agn_edge_fwd32_blocks": (i32, [i32]),
             "agn_edge_forward32": (i32, [C.POINTER(EdgeFwdArgs), vp]),
+            "agn_edge_agg_fixup": (i32, [C.POINTER(EdgeFwdArgs), vp]),
+            "agn_debug_edge_agg_launches": (C.c_long, []),
             "agn_debug_node32_launches": (C.c_long, []),
             "agn_debug_enc32_launches": (C.c_long, []),
             "agn_debug_dec32_launches": (C.c_long, []),

@@ -333,10 +333,22 @@ def edge_saves_ok():
     return os.environ.get("AEROGNN_EB_SAVED", "1") != "0"
 
 
-def edge_forward(*, rows, wpk, bias, ln, e, proj, src, dst, out, a1=None, stats=None, tag=None, cost=None):
+def edge_agg_ok(N, aggregation):
+    """The edge forward kernel also forms the receiver sums (agn_edge_forward32 with agg, then
+    agn_edge_agg_fixup), and the node kernel reads them as a plain input instead of walking e' again
+    ("receiver sums inside the edge forward"): sum aggregation on levels the 32-row
+    node kernel covers. AEROGNN_EDGE_AGG=0 keeps the node kernel's walk (bitwise the same outputs)."""
+    import os
+    return os.environ.get("AEROGNN_EDGE_AGG", "1") != "0" and aggregation == "add" and N >= 64 * 1024
+
+
+def edge_forward(*, rows, wpk, bias, ln, e, proj, src, dst, out, a1=None, stats=None, agg=None, rowptr=None,
+                 tag=None, cost=None):
     """agn_edge_forward32: out = e + LN(chain(e, P_s[src] + P_d[dst])) on 32-row tiles (bitwise the
     resident agn_mlp_forward kernel); a1 (AGN_TILED, tiled_empty) and stats ([rows, 2] fp32) are the
-    fused backward's training saves, both or neither."""
+    fused backward's training saves, both or neither. agg ([N, 128], with the CSC rowptr [N + 1] of
+    dst): the receiver sums of out, bitwise segment_sum's; the kernel writes the receivers inside one
+    wave's run of tiles, the agn_edge_agg_fixup launch (tag agg_fixup) the few that cross a run's end."""
     lib = L.lib()
     a = L.EdgeFwdArgs()
     a.rows = int(rows)
@@ -348,8 +360,17 @@ def edge_forward(*, rows, wpk, bias, ln, e, proj, src, dst, out, a1=None, stats=
     a.e, a.proj, a.src, a.dst, a.out = ptr(e), ptr(proj), ptr(src), ptr(dst), ptr(out)
     a.act[0] = ptr(a1)
     a.stats = ptr(stats)
+    if agg is not None:
+        assert agg.dtype == out.dtype and agg.is_contiguous() and agg.shape[1] == 128
+        assert rowptr.dtype == torch.int32 and rowptr.is_contiguous() and rowptr.numel() == agg.shape[0] + 1
+        a.agg, a.rowptr, a.nodes = ptr(agg), ptr(rowptr), int(agg.shape[0])
     with timed(tag, cost):
         check(lib.agn_edge_forward32(C.byref(a), stream()), "edge_forward32")
+    if agg is not None:
+        # at most one receiver per wave of the grid, each read once from out and written once
+        nw = 12 * a.nblk
+        with timed("agg_fixup", (0.0, 0.0, 4 * nw + 256 * out.element_size() * nw)):
+            check(lib.agn_edge_agg_fixup(C.byref(a), stream()), "edge_agg_fixup")
 
 
 # Production-path fault polling: every FAULT_POLL_EVERY fused launches an async copy
@@ -725,8 +746,9 @@ def wgrad_segsum(G, X, dw, rowptr, dst, out, tag="wgrad_edge"):
 #                projection N(3sH) (read x, write P_s|P_d), node kernel N(3sH) (read x, agg, write x');
 #                training = 3x forward, so each backward kernel carries 2x its forward share;
 #   impl_bytes = the bytes this implementation's kernel must move (its own I/O model, cost_* below).
-def alg8d_edge(E, N, H, s, bwd=False):
-    return (2 if bwd else 1) * (E * (2 * s * H + 8) + N * 2 * s * H)
+def alg8d_edge(E, N, H, s, bwd=False, agg=False):
+    # agg: this launch also writes the receiver sums the node kernel's share reads
+    return (2 if bwd else 1) * (E * (2 * s * H + 8) + N * 2 * s * H) + (N * s * H if agg else 0)
 
 
 def alg8d_node(N, H, s, bwd=False, proj=False):
@@ -743,16 +765,21 @@ def mask_bytes(H):
     return 8 * max(1, (H + 63) // 64)
 
 
-def cost_edge_fwd(E, N, H, s, nlin, train, a1_saves=False):
+def cost_edge_fwd(E, N, H, s, nlin, train, a1_saves=False, agg=False):
     """Minimum HBM bytes / MFMA flops of one fused edge-MLP launch (SURVEY §8d, DESIGN.md);
-    a1_saves: agn_edge_forward32's training saves for the fused backward (a1 + statistics)."""
+    a1_saves: agn_edge_forward32's training saves for the fused backward (a1 + statistics);
+    agg: the launch also writes the receiver sums [N, H]."""
     per = 2 * H * s + 8 + ((nlin - 1) * (H * s + mask_bytes(H)) + H * s + 8 if train else 0)
     per += (H * s + 8) if a1_saves else 0
-    return E * per + N * 2 * H * s, 2 * E * H * H * nlin
+    return E * per + N * 2 * H * s + (N * H * s if agg else 0), 2 * E * H * H * nlin
 
 
-def cost_node_fwd(E, N, H, s, nlin, train):
+def cost_node_fwd(E, N, H, s, nlin, train, plain_agg=False):
+    """plain_agg: the receiver sums come in as a plain [N, H] input (read once, not stored again)
+    instead of being walked from the E rows of e'."""
     per = 2 * H * s + 8 + ((nlin - 1) * (H * s + mask_bytes(H)) + 2 * H * s + 8 if train else 0)
+    if plain_agg:
+        return N * (per + H * s - (H * s if train else 0)), 2 * N * H * (2 * H + (nlin - 1) * H)
     return N * per + E * H * s, 2 * N * H * (2 * H + (nlin - 1) * H)
 
 

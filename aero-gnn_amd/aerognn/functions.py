@@ -24,7 +24,7 @@ from . import _lib as L
 from ._lib import check, ptr
 from . import core as _core
 from .core import (Pack, WGrad, alg8d_edge, alg8d_node, with_alg, edge_bwd_fused, fused_edge_train_ok, bwd_nblocks,
-                   edge32_ok, edge_saves_ok, edge_forward,
+                   edge32_ok, edge_saves_ok, edge_agg_ok, edge_forward,
                    cost_edge_bwd_fused,
                    proj_kernel_ok, proj_forward, proj_backward, wgrad_dpd_ok, wgrad_segsum, tiled_empty, relu_mask_empty, colsum_rows, cost_edge_bwd, cost_edge_bwd_cat, cost_edge_fwd,
                    cost_edge_fwd_cat, cost_node_bwd, cost_node_fwd, cost_proj, cost_wec_bwd, cost_wec_fwd, dt_code,
@@ -478,6 +478,10 @@ class GMPFn(torch.autograd.Function):
         # fused training on it: the forward saves a1 and the LayerNorm statistics, and the fused
         # backward starts its recompute from them (AEROGNN_EB_SAVED=0: it recomputes from e, P)
         saved = fused and e32 and edge_saves_ok()
+        # the receiver sums formed by the edge kernel from the tiles it holds; the node kernel then
+        # reads them as a plain input (AEROGNN_EDGE_AGG=0: its walk over e' instead)
+        eagg = e32 and edge_agg_ok(N, spec.aggregation)
+        agg = torch.empty(N, H, dtype=dt, device=dev) if eagg else None
         a1s = tiled_empty(E, H, dt, dev) if saved else None
         sts = torch.empty(E, 2, dtype=torch.float32, device=dev) if saved else None
         ea, ehp, est = _alloc_saves(es, E, dt, dev, train and not fused)
@@ -496,9 +500,10 @@ class GMPFn(torch.autograd.Function):
                             tag="proj", cost=with_alg(alg8d_node(N, H, sz), cost_proj(N, H, sz)))
             if e32:
                 edge_forward(rows=E, wpk=es.wpk(), bias=es.biases(), ln=es.lnp(), e=e, proj=P, src=level.src,
-                             dst=level.dst, out=e_out, a1=a1s, stats=sts,
-                             tag="edge_fwd", cost=with_alg(alg8d_edge(E, N, H, sz), cost_edge_fwd(E, N, H, sz, es.nlin,
-                                                                                                 False, a1_saves=saved)))
+                             dst=level.dst, out=e_out, a1=a1s, stats=sts, agg=agg, rowptr=level.rowptr if eagg else None,
+                             tag="edge_fwd", cost=with_alg(alg8d_edge(E, N, H, sz, agg=eagg),
+                                                           cost_edge_fwd(E, N, H, sz, es.nlin, False, a1_saves=saved,
+                                                                         agg=eagg)))
             else:
                 mlp_forward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H,
                             segs=[(L.SEG_PLAIN, H, e.stride(0), e, None, None)],
@@ -518,18 +523,22 @@ class GMPFn(torch.autograd.Function):
                                                        cost_edge_fwd_cat(E, N, H, x.element_size(), es.nlin, train)))
         # receiver aggregation (mgnLayer.py:144-146): the node kernel's SUM / MEAN input segment
         # walks each receiver's CSC range in edge order (torch_scatter's fp32 order); in training it
-        # also stores the sums for the backward. (A separate segment-sum launch and sums fused into
-        # the edge kernel were measured slower: DESIGN.md §9, round 3.)
+        # also stores the sums for the backward. With eagg the edge kernel has formed the same sums
+        # already and they come in as a plain segment. (A separate segment-sum launch measured
+        # slower, and so did round 3's sums in the resident edge kernel: DESIGN.md §9.)
         kind = L.SEG_MEAN if spec.aggregation == "mean" else L.SEG_SUM
-        agg = torch.empty(N, H, dtype=dt, device=dev) if train else None
-        aseg = (kind, H, e_out.stride(0), e_out, level.rowptr, agg)
+        if eagg:
+            aseg = (L.SEG_PLAIN, H, agg.stride(0), agg, None, None)
+        else:
+            agg = torch.empty(N, H, dtype=dt, device=dev) if train else None
+            aseg = (kind, H, e_out.stride(0), e_out, level.rowptr, agg)
         mlp_forward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H,
                     segs=[(L.SEG_PLAIN, H, x.stride(0), x, None, None), aseg],
                     wpk=ns.wpk(), bias=ns.biases(), ln=ns.lnp(), resid=x, out=x_out,
                     acts=na, hpre=nhp, stats=nst,
                     tag="node_fwd", cost=with_alg(alg8d_node(N, H, x.element_size()),
                                                    cost_node_fwd(E, N, H, x.element_size(),
-                                                                 ns.nlin, train)))
+                                                                 ns.nlin, train, plain_agg=eagg)))
         ctx.spec, ctx.level = spec, level
         ctx.saves = (ea, ehp, est, na, nhp, nst, agg)
         ctx.fused, ctx.proj, ctx.esaves = fused, (P if fused and not saved else None), (a1s, sts)

@@ -26,6 +26,20 @@
 // wave streaming 32-row tiles in CSC order over an XCD-grouped walk; a tile's node ids are loaded
 // one tile ahead through the wave's LDS slot (a loop-carried load result would make the compiler
 // wait vmcnt(0) at the loop head, i.e. for the previous tile's stores too).
+//
+// Receiver sums (AGG, agn_edge_fwd_args.agg): agg[n] = sum of e' rows rowptr[n] .. rowptr[n+1]-1, formed
+// from the finished tile instead of by the node kernel re-reading all of e' from HBM. Each wave walks
+// one contiguous run of tiles (tile32.hpp RangeWalk) in place of the strided walk. The rounded tile
+// goes through a 2-KB LDS buffer of the wave in four 8-row batches beside its global stores; lane l
+// then adds columns 2l, 2l + 1 of the rows in edge order: per receiver and column the fp32 adds of
+// segment_sum4_kernel (graph.hip) from +0, one rounding, a 256-B row store when the receiver's run
+// of edges ends. Where a receiver opens is wave-uniform (one ballot per tile over the dst ids the
+// tile loaded), and the open sum goes from tile to tile. One writer per agg row, nothing passes
+// between waves: a wave writes the receivers whose whole edge range lies inside its run (it reads
+// the dst of the rows next to the run's ends to tell) and zeros for the empty receivers at a row of
+// its run (those past the last edge: the wave with the last tile); a receiver that crosses the end of
+// a run is summed from e' by edge_agg_fixup_kernel, which recomputes the runs from (rows, grid).
+#include <type_traits>
 #include "tile32.hpp"
 #include "aerognn.h"
 
@@ -43,6 +57,9 @@ constexpr int PF = AGN_E32_PF;          // weight fragments in flight
 #define AGN_E32_DIAG 0  // timing diagnostics only (outputs wrong): 1 no LayerNorm statistics, 3 no row sum
 #endif
 
+#ifndef AGN_E32_AGG_DIAG
+#define AGN_E32_AGG_DIAG 0  // timing diagnostics of AGG only (agg wrong): 1 the contiguous walk alone (no stage, no
+#endif                      // sums), 2 everything but the agg stores
 constexpr int NW = 12;  // waves per CU (three per SIMD)
 
 struct Smem {
@@ -51,6 +68,11 @@ struct Smem {
   int ids[NW][64];      // per wave: next tile's src (lanes 0-31) / dst (32-63)
 };
 static_assert(sizeof(Smem) <= 160 * 1024, "LDS budget");
+struct SmemAgg : Smem {
+  uint4 stage[NW][8 * 16];  // per wave: 8 rows of the rounded tile, chunk k of row r at [r][k ^ r]
+};
+static_assert(sizeof(SmemAgg) <= 160 * 1024, "LDS budget");
+typedef const __attribute__((address_space(4))) int32_t* cidx_t;  // index reads as scalar loads
 
 // Lin l's product: the resident kernel's per-accumulator sequence, fragments PF deep (tile32.hpp)
 AGN_DEV void gemm4(f32x16 (&acc)[NT], const BOp<bf16, NR>& b, const uint4* w, int lane) {
@@ -74,10 +96,10 @@ __device__ unsigned long long* agn_e32_stamps;
   } while (0)
 #endif
 
-template <bool SAVE>
+template <bool SAVE, bool AGG>
 __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_args a) {
   constexpr int NTHR = 64 * NW;
-  __shared__ Smem sm;
+  __shared__ std::conditional_t<AGG, SmemAgg, Smem> sm;
   {
     const uint4* const* wp = reinterpret_cast<const uint4* const*>(a.wpk);
     for (int i = threadIdx.x; i < 4 * LAYER; i += NTHR) sm.w[i] = wp[i / LAYER][i % LAYER];
@@ -90,7 +112,7 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
   const int lane0 = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntiles = (a.rows + 31) / 32;
-  const Walk walk(ntiles, w, NW);
+  const std::conditional_t<AGG, RangeWalk, Walk> walk(ntiles, w, NW);
   int* wids = sm.ids[w];
   const int32_t* const idp = lane0 < 32 ? a.src : a.dst;
   auto tile_id = [&](int t) { return idp[min(t * 32 + (lane0 & 31), a.rows - 1)]; };
@@ -100,6 +122,24 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
 #ifdef AGN_E32_STAMPS
   int ntile = 0;
 #endif
+  // AGG: the open receiver (wave-uniform; the one before the run's first row is not this wave's to
+  // write: closed by the previous run, or crossing into this one). Its two column sums and the
+  // tile's dst ids wait in the wave's stage buffer while the chain runs (the buffer is idle then,
+  // and the chain has no three registers to spare): dwords 0-31 dst, 64-127 / 128-191 the sums.
+  int cur = -1;
+  bool skip = true;
+  char* const aggp = reinterpret_cast<char*>(a.agg);
+  auto agg_put = [&](int n, uint32_t v, int l) {
+    if (AGN_E32_AGG_DIAG == 0 && (unsigned)n < (unsigned)a.nodes)
+      *reinterpret_cast<uint32_t*>(aggp + (size_t)n * (2 * H) + (uint32_t)(4 * l)) = v;
+  };
+  uint32_t* park = nullptr;
+  if constexpr (AGG && AGN_E32_AGG_DIAG != 1) {
+    park = reinterpret_cast<uint32_t*>(sm.stage[w]);
+    if (walk.first < walk.end && walk.first > 0) cur = ((cidx_t)(uintptr_t)a.dst)[walk.first * 32 - 1];
+    park[64 + lane0] = 0u;
+    park[128 + lane0] = 0u;
+  }
   for (int tile = walk.first; tile < walk.end; tile += walk.step) {
     cbarrier();
     E32_STAMP(0);
@@ -116,6 +156,7 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
     BOp<bf16, NR> b;
     {
       const int cs = wids[c], cd = wids[32 + c];
+      if constexpr (AGG && AGN_E32_AGG_DIAG != 1) park[c] = cd;
       if (more) wids[lane] = nid;  // (this tile's reads of the slot are done: LDS is in order per wave)
       // acc = P_s[src] + P_d[dst] on the matrix cores (exact fp32 add, common.hpp acc_add2_mfma)
       uint4 rs[NR / 8], rd[NR / 8];
@@ -192,11 +233,68 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
       ident_frags(f0, f1, lane);
       acc_add2_mfma<NT, NR>(acc, lnb, e0, f0, f1);
     }
+    if constexpr (!AGG || AGN_E32_AGG_DIAG == 1) {
 #pragma unroll
-    for (int i = 0; i < NR / 8; ++i) {
-      float v[8];
-      acc_get8(v, acc, i);
-      store8_w(op, i, h, v, valid);
+      for (int i = 0; i < NR / 8; ++i) {
+        float v[8];
+        acc_get8(v, acc, i);
+        store8_w(op, i, h, v, valid);
+      }
+    } else {
+      u32x4 pk[NR / 8];  // chunk 2i + h of row c, as stored
+#pragma unroll
+      for (int i = 0; i < NR / 8; ++i) {
+        float v[8];
+        acc_get8(v, acc, i);
+        pk[i] = __builtin_bit_cast(u32x4, pack8_w(v, h));
+        if (valid) *reinterpret_cast<u32x4*>(op + 16 * i + 8 * h) = pk[i];
+      }
+      char* const stg = reinterpret_cast<char*>(sm.stage[w]);
+      const int rcv = (int)park[c];  // the receiver of row c
+      // bit c of brk: row c opens another receiver than the row before it (row 0: than the open one);
+      // bit c of live: row c is a row of the matrix (a partial last tile)
+      const int before = c > 0 ? (int)park[c - 1] : cur;
+      const int nrow = min(32, a.rows - tile * 32);
+      const uint32_t live = nrow >= 32 ? ~0u : (1u << nrow) - 1u;
+      const uint32_t brk = (uint32_t)__ballot(rcv != before) & live;
+      f32x2 s = {__uint_as_float(park[64 + lane]), __uint_as_float(park[128 + lane])};
+      const uint32_t wr = (uint32_t)(c & 7) * 256u, wx = (uint32_t)(c & 7) << 4;
+      const uint32_t rd = (uint32_t)lane << 2;  // dword `lane` of a row: chunk lane / 4
+#pragma unroll 1
+      for (int p = 0; p < 4; ++p) {
+        // (LDS is in order per wave: the batch's reads see its writes, the next batch's writes
+        // come after these reads)
+        if ((c >> 3) == p) {
+#pragma unroll
+          for (int i = 0; i < NR / 8; ++i)
+            *reinterpret_cast<u32x4*>(stg + wr + (((uint32_t)(2 * i + h) << 4) ^ wx)) = pk[i];
+        }
+        uint32_t x[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) x[r] = *reinterpret_cast<const uint32_t*>(stg + r * 256 + (rd ^ (uint32_t)(r << 4)));
+        const uint32_t bb = (brk >> (8 * p)) & 0xffu, lb = (live >> (8 * p)) & 0xffu;
+        if (bb == 0u && lb == 0xffu) {  // eight rows of the open receiver
+#pragma unroll
+          for (int r = 0; r < 8; ++r) s += f32x2{lo_bf16(x[r]), hi_bf16(x[r])};
+        } else {
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            if ((lb >> r) & 1u) {
+              if ((bb >> r) & 1u) {
+                const int d = __builtin_amdgcn_readlane(rcv, 8 * p + r);
+                if (!skip) agg_put(cur, pack2(s[0], s[1]), lane);
+                for (int n = cur + 1; n < d; ++n) agg_put(n, 0u, lane);  // the empty receivers at this row
+                cur = d;
+                skip = false;
+                s = f32x2{0.f, 0.f};
+              }
+              s += f32x2{lo_bf16(x[r]), hi_bf16(x[r])};
+            }
+          }
+        }
+      }
+      park[64 + lane] = __float_as_uint(s[0]);
+      park[128 + lane] = __float_as_uint(s[1]);
     }
 
     E32_STAMP(7);
@@ -204,11 +302,62 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
     ++ntile;
 #endif
   }
+  if constexpr (AGG && AGN_E32_AGG_DIAG != 1) {
+    if (walk.first < walk.end) {
+      cbarrier();
+      const uint32_t sum = pack2(__uint_as_float(park[64 + lane0]), __uint_as_float(park[128 + lane0]));
+      const int rend = min(walk.end * 32, a.rows);
+      if (rend == a.rows) {  // the last edge: its receiver ends here, the rest are empty
+        if (!skip) agg_put(cur, sum, lane0);
+        for (int n = cur + 1; n < a.nodes; ++n) agg_put(n, 0u, lane0);
+      } else if (!skip && ((cidx_t)(uintptr_t)a.dst)[rend] != cur) {
+        agg_put(cur, sum, lane0);  // ends with the run (the empty ones after it: the next run's)
+      }
+    }
+  }
 }
+
+// The receivers edge32_fwd_kernel<., true> left out: one wave per wave of that grid. A run that
+// starts inside a receiver's edge range (the rows on both sides of its first row have one dst) makes
+// that receiver a crossing one; the first such run of a receiver sums it from e' over its whole
+// rowptr range, lane l columns 2l, 2l + 1 in edge order (segment_sum4_kernel's adds), 4 rows in flight.
+__global__ __launch_bounds__(256) void edge_agg_fixup_kernel(const agn_edge_fwd_args a) {
+  const int lane = threadIdx.x & 63;
+  const int gw = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (gw >= a.nblk * NW) return;
+  const int ntiles = (a.rows + 31) / 32;
+  const RangeWalk run(ntiles, a.nblk, gw / NW, gw % NW, NW);
+  if (run.first >= run.end || run.first == 0) return;
+  const cidx_t dst = (cidx_t)(uintptr_t)a.dst, ptr = (cidx_t)(uintptr_t)a.rowptr;
+  const int p = run.first * 32;
+  const int n = dst[p];
+  if (dst[p - 1] != n || (unsigned)n >= (unsigned)a.nodes) return;
+  const int beg = min(max(ptr[n], 0), a.rows), end = min(max(ptr[n + 1], beg), a.rows);
+  // an earlier run that also starts inside n has it
+  if (RangeWalk::first_of(ntiles, a.nblk, NW, run.first - 1) * 32 > beg) return;
+  const char* ep = reinterpret_cast<const char*>(a.out) + (uint32_t)(4 * lane);
+  float s0 = 0.f, s1 = 0.f;
+  for (int j = beg; j < end; j += 4) {
+    uint32_t v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const uint32_t*>(ep + (size_t)min(j + q, end - 1) * (2 * H));
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (j + q < end) {
+        s0 += lo_bf16(v[q]);
+        s1 += hi_bf16(v[q]);
+      }
+  }
+  *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.agg) + (size_t)n * (2 * H) + (uint32_t)(4 * lane)) = pack2(s0, s1);
+}
+
+long g_agg_launches = 0;  // launches that formed the receiver sums (agn_debug_edge_agg_launches: tests check the dispatch)
 
 }  // namespace
 
 extern "C" {
+
+long agn_debug_edge_agg_launches(void) { return g_agg_launches; }
 
 #ifdef AGN_E32_STAMPS
 int agn_debug_e32_stamps(void* p) {
@@ -222,7 +371,11 @@ int agn_edge_fwd32_blocks(int rows) {
 
 int agn_edge_forward32(const agn_edge_fwd_args* a, void* stream) {
   if (!a || a->rows < 0 || a->nblk < 1) return AGN_E_ARG;
-  if (a->rows == 0) return 0;
+  if (a->rows == 0) {  // no edge: every receiver is empty
+    if (a->agg && a->nodes > 0 && hipMemsetAsync(a->agg, 0, (size_t)a->nodes * (2 * H), (hipStream_t)stream) != hipSuccess)
+      return launch_status();
+    return 0;
+  }
   if (!a->e || !a->proj || !a->src || !a->dst || !a->out || !a->ln_g || !a->ln_b) return AGN_E_ARG;
   if (a->act[1] || a->act[2] || a->hpre) return AGN_E_ARG;  // a1 and the statistics are the only saves
   const bool save = a->act[0] != nullptr;
@@ -231,8 +384,26 @@ int agn_edge_forward32(const agn_edge_fwd_args* a, void* stream) {
   for (int l = 0; l < 4; ++l)
     if (!a->wpk[l] || !al16(a->wpk[l])) return AGN_E_ARG;
   if (!al16(a->e) || !al16(a->proj) || !al16(a->out)) return AGN_E_ARG;
-  if (save) hipLaunchKernelGGL(edge32_fwd_kernel<true>, dim3(a->nblk), dim3(64 * NW), 0, (hipStream_t)stream, *a);
-  else hipLaunchKernelGGL(edge32_fwd_kernel<false>, dim3(a->nblk), dim3(64 * NW), 0, (hipStream_t)stream, *a);
+  if (a->agg && (!a->rowptr || a->nodes < 1 || !al16(a->agg))) return AGN_E_ARG;
+  const dim3 g(a->nblk), blk(64 * NW);
+  hipStream_t st = (hipStream_t)stream;
+  if (a->agg) {
+    ++g_agg_launches;
+    if (save) hipLaunchKernelGGL((edge32_fwd_kernel<true, true>), g, blk, 0, st, *a);
+    else hipLaunchKernelGGL((edge32_fwd_kernel<false, true>), g, blk, 0, st, *a);
+  } else {
+    if (save) hipLaunchKernelGGL((edge32_fwd_kernel<true, false>), g, blk, 0, st, *a);
+    else hipLaunchKernelGGL((edge32_fwd_kernel<false, false>), g, blk, 0, st, *a);
+  }
+  return launch_status();
+}
+
+int agn_edge_agg_fixup(const agn_edge_fwd_args* a, void* stream) {
+  if (!a || a->rows < 0 || a->nblk < 1 || a->nblk > (1 << 20)) return AGN_E_ARG;
+  if (!a->agg || !a->rowptr || a->nodes < 1 || !al16(a->agg)) return AGN_E_ARG;
+  if (a->rows == 0) return 0;
+  if (!a->dst || !a->out || !al16(a->out)) return AGN_E_ARG;
+  hipLaunchKernelGGL(edge_agg_fixup_kernel, dim3((a->nblk * NW + 3) / 4), dim3(256), 0, (hipStream_t)stream, *a);
   return launch_status();
 }
 

@@ -16,6 +16,11 @@
 // sums reach the operand layout through a 2-KB LDS buffer, then the chain runs on the MFMA as
 // edge32_fwd.hip's does. C3 level-0 node MLP: 378 against 453 us per launch for the per-lane walk at
 // 12 waves (profiles/r5_node32_walk_ab.txt), 490 us for the general kernel.
+//
+// PLAIN: the second segment is a plain [rows][128] input, the receiver sums already formed
+// (agn_edge_forward32 with agg + agn_edge_agg_fixup): the walk is replaced by the row's 16-B loads
+// (BOp::load_w, as for x), everything after it is the same, so the outputs and saves are bitwise the
+// SUM variant's on the sums' source rows.
 #include "tile32.hpp"
 #include "aerognn.h"
 
@@ -53,7 +58,7 @@ static_assert(sizeof(Smem<4>) <= 160 * 1024, "LDS budget");
 
 // SAVES: the training saves of agn_mlp_fwd_args (relu outputs act[0..1] with their AGN_RELU_MASK
 // bits, hpre, stats; row-major or AGN_TILED as a.tiled says), as the general kernel writes them
-template <int NLIN, bool SAVES>
+template <int NLIN, bool SAVES, bool PLAIN>
 __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_args a) {
   constexpr int NTHR = 64 * NW;
   __shared__ Smem<NLIN> sm;
@@ -83,7 +88,9 @@ __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_a
   const int32_t* const rowptr = sg.index;
   // lane l <= 32 loads rowptr[32 t + l] (clamped: a partial last tile's rows past the end are empty)
   auto tile_rp = [&](int t) { return rowptr[min(t * 32 + min(lane0, 32), a.rows)]; };
-  if (walk.first < walk.end) wrp[lane0] = tile_rp(walk.first);
+  if constexpr (!PLAIN) {
+    if (walk.first < walk.end) wrp[lane0] = tile_rp(walk.first);
+  }
   const bf16* X = reinterpret_cast<const bf16*>(sx.ptr);
   const bf16* EP = reinterpret_cast<const bf16*>(sg.ptr);
   for (int tile = walk.first; tile < walk.end; tile += walk.step) {
@@ -94,7 +101,8 @@ __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_a
     const bool valid = row < a.rows;
     const int rr = valid ? row : a.rows - 1;
     const bool more = tile + walk.step < walk.end;
-    const int nrp = tile_rp(more ? tile + walk.step : tile);
+    int nrp = 0;
+    if constexpr (!PLAIN) nrp = tile_rp(more ? tile + walk.step : tile);
     // ---- agg: each node's e' rows in edge order, fp32, one rounding (mlp.hip walk2_segment's
     // values). The rows are read coalesced: lane group g = lane / 16 walks one node of a round,
     // lane k = lane % 16 loads chunk k (16 B) of each of its rows, so one load instruction covers 4
@@ -102,7 +110,17 @@ __global__ __launch_bounds__(64 * NW) void node32_fwd_kernel(const agn_mlp_fwd_a
     // reach the owning lanes (node c: lanes c and c + 32, the operand layout) through the wave's
     // 2-KB LDS buffer, 8 nodes per batch.
     BOp<bf16, NR> bagg;
-    {
+    if constexpr (PLAIN) {
+      // (a partial last tile's rows past the end take the last row's sums, as the walk does)
+      bagg.load_w(EP + (size_t)rr * sg.ld, h);
+#pragma unroll
+      for (int i = 0; i < NR / 8; ++i) {
+        u32x4 t = __builtin_bit_cast(u32x4, bagg.u[i]);
+        asm volatile("" : "+v"(t));
+        bagg.u[i] = __builtin_bit_cast(bf16x8, t);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    } else {
       const int g = lane >> 4, k = lane & 15;
       char* buf = sm.agg[w];
       uint4 mine[NR / 8];
@@ -300,7 +318,9 @@ bool node32_fwd_try(const agn_mlp_fwd_args* a, void* stream, int* rc) {
   const agn_seg& sx = a->seg[0];
   const agn_seg& sg = a->seg[1];
   if (sx.kind != AGN_SEG_PLAIN || sx.k != H || sx.ld % 8 || !sx.ptr) return false;
-  if ((sg.kind != AGN_SEG_SUM && sg.kind != AGN_SEG_MEAN) || sg.k != H || sg.ld % 8 || !sg.ptr || !sg.index) return false;
+  const bool plain = sg.kind == AGN_SEG_PLAIN;  // the sums as a plain input (no index, nothing to store)
+  if ((!plain && sg.kind != AGN_SEG_SUM && sg.kind != AGN_SEG_MEAN) || sg.k != H || sg.ld % 8 || !sg.ptr) return false;
+  if (plain ? sg.store != nullptr : !sg.index) return false;
   if (a->resid != sx.ptr || a->out_ld != sx.ld || a->out_ld % 8) return false;
   // training saves: ReLU outputs (+ mask bits), hpre, stats (no pre-activations: ReLU only)
   bool saves = a->hpre || a->stats;
@@ -315,12 +335,20 @@ bool node32_fwd_try(const agn_mlp_fwd_args* a, void* stream, int* rc) {
   if (!al16(sx.ptr) || !al16(sg.ptr) || !al16(a->out) || !al16(sg.store)) return false;
   const dim3 g(tile_blocks((a->rows + 31) / 32, NW)), blk(64 * NW);
   hipStream_t st = (hipStream_t)stream;
-  if (a->nlin == 4) {
-    if (saves) hipLaunchKernelGGL((node32_fwd_kernel<4, true>), g, blk, 0, st, *a);
-    else hipLaunchKernelGGL((node32_fwd_kernel<4, false>), g, blk, 0, st, *a);
+  if (plain) {
+    if (a->nlin == 4) {
+      if (saves) hipLaunchKernelGGL((node32_fwd_kernel<4, true, true>), g, blk, 0, st, *a);
+      else hipLaunchKernelGGL((node32_fwd_kernel<4, false, true>), g, blk, 0, st, *a);
+    } else {
+      if (saves) hipLaunchKernelGGL((node32_fwd_kernel<3, true, true>), g, blk, 0, st, *a);
+      else hipLaunchKernelGGL((node32_fwd_kernel<3, false, true>), g, blk, 0, st, *a);
+    }
+  } else if (a->nlin == 4) {
+    if (saves) hipLaunchKernelGGL((node32_fwd_kernel<4, true, false>), g, blk, 0, st, *a);
+    else hipLaunchKernelGGL((node32_fwd_kernel<4, false, false>), g, blk, 0, st, *a);
   } else {
-    if (saves) hipLaunchKernelGGL((node32_fwd_kernel<3, true>), g, blk, 0, st, *a);
-    else hipLaunchKernelGGL((node32_fwd_kernel<3, false>), g, blk, 0, st, *a);
+    if (saves) hipLaunchKernelGGL((node32_fwd_kernel<3, true, false>), g, blk, 0, st, *a);
+    else hipLaunchKernelGGL((node32_fwd_kernel<3, false, false>), g, blk, 0, st, *a);
   }
   ++g_launches;
   *rc = launch_status();

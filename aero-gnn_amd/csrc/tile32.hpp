@@ -44,6 +44,48 @@ struct Walk {
   }
 };
 
+// The same tiles as contiguous ranges: the waves of an XCD group split their eighth of the tiles
+// (all tiles when the grid is no multiple of 8) into one run each, the first `cnt % waves` runs one
+// tile longer. A wave that walks its run in order can carry a sum over the rows from tile to tile
+// (edge32_fwd.hip's receiver sums). The split is a function of (ntiles, grid, block, w, nw) alone, so
+// another launch can recompute every run's ends (agn_edge_agg_fixup).
+struct RangeWalk {
+  int first, end, step;
+  // the tiles [base, base + cnt) that block blk's group splits over n runs, and this wave's run i
+  static AGN_DEV void group(int ntiles, int grid, int blk, int w, int nw, int& base, int& cnt, int& i, int& n) {
+    if (grid >= 8 && (grid & 7) == 0) {
+      const int per = (ntiles + 7) / 8;
+      base = (blk & 7) * per;
+      cnt = max(0, min(ntiles, base + per) - base);
+      i = (blk >> 3) * nw + w;
+      n = (grid >> 3) * nw;
+    } else {
+      base = 0;
+      cnt = ntiles;
+      i = blk * nw + w;
+      n = grid * nw;
+    }
+  }
+  AGN_DEV RangeWalk(int ntiles, int grid, int blk, int w, int nw) {
+    int base, cnt, i, n;
+    group(ntiles, grid, blk, w, nw, base, cnt, i, n);
+    const int q = cnt / n, r = cnt - q * n;
+    first = base + i * q + min(i, r);
+    end = first + q + (i < r ? 1 : 0);
+    step = 1;
+  }
+  AGN_DEV RangeWalk(int ntiles, int w, int nw) : RangeWalk(ntiles, (int)gridDim.x, (int)blockIdx.x, w, nw) {}
+  // the first tile of the run that holds tile t < ntiles
+  static AGN_DEV int first_of(int ntiles, int grid, int nw, int t) {
+    int base, cnt, i, n;
+    const bool xcd = grid >= 8 && (grid & 7) == 0;
+    group(ntiles, grid, xcd ? t / ((ntiles + 7) / 8) : 0, 0, nw, base, cnt, i, n);
+    const int q = cnt / n, r = cnt - q * n, o = t - base;
+    const int k = o < r * (q + 1) ? o / (q + 1) : r + (o - r * (q + 1)) / q;  // (q >= 1 here: o < cnt)
+    return base + k * q + min(k, r);
+  }
+};
+
 // acc[ot] += W[output tile ot0 + ot, k-units u0 .. u0 + 7] . b over the k-steps in order (the
 // per-accumulator sequence of common.hpp gemm, so the sums are bitwise the general kernel's). w is
 // a packed image of ku_total k-units per output tile, in LDS or in global memory (L2); its

@@ -461,15 +461,30 @@ typedef struct {
   void* act[3];              /* training saves: act[0] = a1 in AGN_TILED (rows padded to 32); act[1..2] NULL */
   void* hpre;                /* must be NULL */
   float* stats;              /* training saves: [rows][2] LayerNorm (mean, rstd), or NULL */
+  /* receiver sums formed in the kernel (agg == NULL: not formed, rowptr and nodes unused) */
+  void* agg;                 /* [nodes][128]: agg[n] = sum of out's rows rowptr[n] .. rowptr[n+1]-1 */
+  const int32_t* rowptr;     /* [nodes + 1] CSC row pointer of dst (rows grouped by receiver, ascending) */
+  int nodes;
+  int _pad;
 } agn_edge_fwd_args;
 /* The chain on 32-edge tiles with 32x32x16 MFMAs, bitwise agn_mlp_forward's resident kernel
  * on the same operands: the forward of the training step (fused backward) and of inference.
  * Grid agn_edge_fwd32_blocks(rows). Replaces mlp.py:37-60 MLP.forward on EdgeBlockSum's chain
  * (mgnLayer.py:72-105, residual :205). With act[0] and stats set (training) it also saves the
  * first ReLU output a1 (AGN_TILED) and the LayerNorm statistics, which agn_edge_bwd_fused reads
- * instead of recomputing h0 from e and the projection rows. */
+ * instead of recomputing h0 from e and the projection rows.
+ * With agg set the kernel also forms the receiver sums of e' (mgnLayer.py:144-146 scatter_add) from
+ * the tiles it holds: each wave walks one contiguous run of tiles and writes every receiver whose
+ * edge range lies inside its run, per column the fp32 adds of agn_segment_sum from +0 in edge
+ * order with one rounding, and zeros for the empty receivers; agg need not be initialised. A
+ * receiver whose range crosses the end of a run is left to agn_edge_agg_fixup, which must follow on
+ * the same stream with the same arguments: it sums those (at most one per wave of the grid) from
+ * out. After both, agg is bitwise agn_segment_sum(out). */
 int agn_edge_fwd32_blocks(int rows);
 int agn_edge_forward32(const agn_edge_fwd_args* a, void* stream);
+int agn_edge_agg_fixup(const agn_edge_fwd_args* a, void* stream);
+/* testing: agn_edge_forward32 launches so far that formed the receiver sums (agg set) */
+long agn_debug_edge_agg_launches(void);
 /* dw[m][k] = sum_s dw_partial[s][m][k] (and db) for each desc: the fixed-order second stage
  * of agn_wgrad on caller-provided slabs (m, k <= 128 per desc here) */
 int agn_wgrad_reduce(const agn_wgrad_batch* b, int nsplit, void* stream);
