@@ -90,7 +90,7 @@ class EdgeBwdArgs(C.Structure):
 class EdgeFwdArgs(C.Structure):
     _fields_ = [("rows", i32), ("nblk", i32), ("wpk", vp * 4), ("bias", vp * 4), ("ln_g", vp), ("ln_b", vp),
                 ("e", vp), ("proj", vp), ("src", vp), ("dst", vp), ("out", vp), ("act", vp * 3), ("hpre", vp),
-                ("stats", vp), ("agg", vp), ("rowptr", vp), ("nodes", i32), ("_pad", i32)]
+                ("stats", vp), ("agg", vp), ("rowptr", vp), ("nodes", i32), ("agg_mean", i32)]
 
 
 class PackDesc(C.Structure):

@@ -342,13 +342,28 @@ def edge_agg_ok(N, aggregation):
     return os.environ.get("AEROGNN_EDGE_AGG", "1") != "0" and aggregation == "add" and N >= 64 * 1024
 
 
+def v2_edge32_ok(dtype, hidden, nlin, has_ln, act, E, N, train):
+    """MeshGraphNetLayer_v2 (models/trial1.py) runs its edge update on agn_edge_forward32's
+    projection-free instantiation with the receiver means formed there, and in training its backward
+    on agn_edge_bwd_fused from the forward's saves: the bf16 H = 128 ReLU chain of 4 Linears + LN on
+    levels of >= 65,536 edges and nodes (fused_edge_train_ok's and edge_agg_ok's thresholds).
+    AEROGNN_V2_EDGE32=0, or in training AEROGNN_EB_SAVED=0 / AEROGNN_FUSED_EDGE_BWD=0 (the fused
+    backward of this chain has no projection rows to recompute from), select the general kernels."""
+    import os
+    return (os.environ.get("AEROGNN_V2_EDGE32", "1") != "0" and edge32_ok(dtype, hidden, nlin, has_ln, act)
+            and E >= 64 * 1024 and N >= 64 * 1024
+            and (not train or (fused_edge_train_ok(E, dtype, hidden, nlin, has_ln) and edge_saves_ok())))
+
+
 def edge_forward(*, rows, wpk, bias, ln, e, proj, src, dst, out, a1=None, stats=None, agg=None, rowptr=None,
-                 tag=None, cost=None):
+                 mean=False, tag=None, cost=None):
     """agn_edge_forward32: out = e + LN(chain(e, P_s[src] + P_d[dst])) on 32-row tiles (bitwise the
     resident agn_mlp_forward kernel); a1 (AGN_TILED, tiled_empty) and stats ([rows, 2] fp32) are the
     fused backward's training saves, both or neither. agg ([N, 128], with the CSC rowptr [N + 1] of
     dst): the receiver sums of out, bitwise segment_sum's; the kernel writes the receivers inside one
-    wave's run of tiles, the agn_edge_agg_fixup launch (tag agg_fixup) the few that cross a run's end."""
+    wave's run of tiles, the agn_edge_agg_fixup launch (tag agg_fixup) the few that cross a run's end.
+    mean: agg holds the receiver means (segment_sum's mean=True). proj None: the projection-free chain
+    out = e + LN(chain(e W0^T + bias[0])) (src unused, dst only with agg)."""
     lib = L.lib()
     a = L.EdgeFwdArgs()
     a.rows = int(rows)
@@ -364,6 +379,7 @@ def edge_forward(*, rows, wpk, bias, ln, e, proj, src, dst, out, a1=None, stats=
         assert agg.dtype == out.dtype and agg.is_contiguous() and agg.shape[1] == 128
         assert rowptr.dtype == torch.int32 and rowptr.is_contiguous() and rowptr.numel() == agg.shape[0] + 1
         a.agg, a.rowptr, a.nodes = ptr(agg), ptr(rowptr), int(agg.shape[0])
+        a.agg_mean = int(bool(mean))
     with timed(tag, cost):
         check(lib.agn_edge_forward32(C.byref(a), stream()), "edge_forward32")
     if agg is not None:

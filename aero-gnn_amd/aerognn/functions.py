@@ -3,6 +3,7 @@
   MLPFn        models/mlp.py:40-51 (encoders, decoder, any MLP)
   FourierEmbedFn  models/fouriermgn.py:111-151, :167-170 ([x | Fourier features] of the node input)
   GMPFn        models/mgnLayer.py:177-213 (EdgeBlockSum / EdgeBlock + NodeBlock + residuals)
+  MGNv2Fn      models/trial1.py:61-73 (MeshGraphNetLayer_v2: projection-free edge update, scatter_mean)
   PoolNodeFn   bsms_mgn.py:265-267 scatter_mean of node latents (and pos)
   PoolEdgeFn   bsms_mgn.py:283     scatter_mean of edge latents over coalesced edges
   UnpoolFn     bsms_mgn.py:199-200,303-306 coarse[f2c] + skip
@@ -663,6 +664,138 @@ class GMPFn(torch.autograd.Function):
                                             ea, part_e, nb_e, tag="wgrad_edge")
         grads_node = _chain_param_grads(ns, gpre_n, [x, agg], na, part_n, nb_n, tag="wgrad_node")
         return (dx, de, None, None, None, *grads_edge, *grads_node)
+
+
+# --------------------------------------------------------------------------- MeshGraphNetLayer_v2
+class V2LayerSpec:
+    """Binds a MeshGraphNetLayer_v2 (models/trial1.py:55-73) to packed operands: edge_mlp and node_mlp
+    are Linear / ReLU chains with a bias on every Linear and a LayerNorm, given as
+    ([(weight, bias), ...], (gamma, beta)) each; the node chain reads cat[x, agg] (2H wide)."""
+
+    def __init__(self, edge, node):
+        self.pack = Pack()
+        H = edge[0][0][0].shape[0]
+        if H not in (32, 64, 128):
+            raise NotImplementedError(f"aerognn kernels support hidden 32/64/128, got {H}")
+        self.H = H
+        self.edge = ChainSpec(edge[0], edge[1], H, self.pack, "e")
+        self.node = ChainSpec(node[0], node[1], H, self.pack, "n")
+        for c in (self.edge, self.node):
+            c.check_hidden()
+            if c.out_dim != H or c.ln is None:
+                raise NotImplementedError("aerognn MeshGraphNetLayer_v2 kernels need H-wide chains with a LayerNorm")
+        if self.edge.in_dim != H or self.node.in_dim != 2 * H:
+            raise NotImplementedError("aerognn MeshGraphNetLayer_v2 kernels need edge_mlp H -> H and node_mlp 2H -> H")
+
+    def params(self):
+        return self.edge.params() + self.node.params()
+
+
+class MGNv2Fn(torch.autograd.Function):
+    """e' = e + edge_mlp(e), x' = x + node_mlp(cat[x, scatter_mean(e', col)]) (trial1.py:61-73) on a
+    CSC-ordered level. Large bf16 H = 128 levels (core.v2_edge32_ok): the edge update and the receiver
+    means are one agn_edge_forward32 launch (+ the fix-up) of the projection-free instantiation, the
+    node kernel reads the means as a plain input, and the training backward of the edge chain is
+    agn_edge_bwd_fused on the forward's a1 and LayerNorm statistics, dW0 = G0^T e and db0 on
+    agn_wgrad. Everything else: the general agn_mlp_forward / agn_mlp_backward / agn_wgrad kernels,
+    the edge chain one plain segment with resid = e, the node chain's SEG_MEAN walk over e'."""
+
+    @staticmethod
+    def forward(ctx, x, e, level, spec: V2LayerSpec, train, *params):
+        require_device(x, e)
+        x, e = _c(x), _c(e)
+        dt, dev = x.dtype, x.device
+        N, E, H = x.shape[0], e.shape[0], spec.H
+        es, ns = spec.edge, spec.node
+        sz = x.element_size()
+        e_out = torch.empty_like(e)
+        x_out = torch.empty_like(x)
+        fast = _core.v2_edge32_ok(dt, H, es.nlin, True, es.act, E, N, train) and e.stride(0) == H
+        na, nhp, nst = _alloc_saves(ns, N, dt, dev, train)
+        ea = ehp = est = a1s = sts = None
+        if fast:
+            agg = torch.empty(N, H, dtype=dt, device=dev)
+            if train:
+                a1s = tiled_empty(E, H, dt, dev)
+                sts = torch.empty(E, 2, dtype=torch.float32, device=dev)
+            edge_forward(rows=E, wpk=es.wpk(), bias=es.biases(), ln=es.lnp(), e=e, proj=None, src=None, dst=level.dst,
+                         out=e_out, a1=a1s, stats=sts, agg=agg, rowptr=level.rowptr, mean=True, tag="edge_fwd",
+                         cost=with_alg(alg8d_edge(E, 0, H, sz, agg=True),
+                                       cost_edge_fwd(E, 0, H, sz, es.nlin, False, a1_saves=train, agg=True)))
+            aseg = (L.SEG_PLAIN, H, agg.stride(0), agg, None, None)
+        else:
+            ea, ehp, est = _alloc_saves(es, E, dt, dev, train)
+            mlp_forward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H,
+                        segs=[(L.SEG_PLAIN, H, e.stride(0), e, None, None)], wpk=es.wpk(), bias=es.biases(),
+                        ln=es.lnp(), resid=e, out=e_out, acts=ea, hpre=ehp, stats=est, tag="edge_fwd",
+                        cost=with_alg(alg8d_edge(E, 0, H, sz), cost_edge_fwd(E, 0, H, sz, es.nlin, train)))
+            # scatter_mean (trial1.py:68): the node kernel's MEAN segment walks each receiver's CSC range
+            # in edge order and, in training, stores the means for the weight gradient
+            agg = torch.empty(N, H, dtype=dt, device=dev) if train else None
+            aseg = (L.SEG_MEAN, H, e_out.stride(0), e_out, level.rowptr, agg)
+        mlp_forward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H,
+                    segs=[(L.SEG_PLAIN, H, x.stride(0), x, None, None), aseg],
+                    wpk=ns.wpk(), bias=ns.biases(), ln=ns.lnp(), resid=x, out=x_out, acts=na, hpre=nhp, stats=nst,
+                    tag="node_fwd", cost=with_alg(alg8d_node(N, H, sz),
+                                                   cost_node_fwd(E, N, H, sz, ns.nlin, train, plain_agg=fast)))
+        ctx.spec, ctx.level, ctx.fast = spec, level, fast
+        ctx.saves = (ea, ehp, est, na, nhp, nst, agg, a1s, sts)
+        ctx.save_for_backward(x, e)
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None: read as zero
+        return x_out, e_out
+
+    @staticmethod
+    def backward(ctx, gx, ge):
+        x, e = ctx.saved_tensors
+        spec, lv = ctx.spec, ctx.level
+        ea, ehp, est, na, nhp, nst, agg, a1s, sts = ctx.saves
+        es, ns = spec.edge, spec.node
+        dt, dev = x.dtype, x.device
+        N, E, H = x.shape[0], e.shape[0], spec.H
+        sz = x.element_size()
+        gx = _c(gx) if gx is not None else torch.zeros_like(x)
+        ge = _c(ge) if ge is not None else None
+        # ---- node chain: d(x) with the residual, d(agg)
+        gpre_n = _alloc_gpre(ns, N, dt, dev)
+        dx = torch.empty_like(x)
+        dagg = torch.empty(N, H, dtype=dt, device=dev)
+        nb_n = bwd_nblocks(N)
+        part_n = torch.empty(nb_n, 2 * H, dtype=torch.float32, device=dev)
+        nb_n = mlp_backward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H, in_dim=2 * H,
+                            wtpk=ns.wtpk(), acts=na, g=gx, gpre=gpre_n, ln_g=ns.lnp()[0], hpre=nhp, stats=nst,
+                            din=[(H, dx, True), (H, dagg, False)], ln_partial=part_n, tag="node_bwd",
+                            cost=with_alg(alg8d_node(N, H, sz, bwd=True), cost_node_bwd(N, H, sz, ns.nlin)))
+        # scatter_mean backward: / max(deg, 1)
+        dagg = gather_rows(N, H, None, dagg, torch.empty_like(dagg), cnt_ptr=lv.rowptr)
+        # ---- edge chain: d(e) = chain gradient + the residual's (ge + dagg[dst])
+        de = torch.empty_like(e)
+        if ctx.fast:
+            g0 = torch.empty(E, H, dtype=dt, device=dev)
+            dW13, db13, part_e, nb_e = edge_bwd_fused(
+                rows=E, wpk=es.wpk(), wtpk0=es.wtpk()[0], bias=es.biases(), ln_g=es.lnp()[0], e=None, proj=None,
+                src=None, dst=lv.dst, g=ge, g2=dagg, de=de, g0=g0, tag="edge_bwd", a1=a1s, stats=sts,
+                cost=with_alg(alg8d_edge(E, 0, H, sz, bwd=True), cost_edge_bwd_fused(E, N, H, sz, saved=True)))
+            dw0 = torch.empty(H, H, dtype=torch.float32, device=dev)
+            db0 = torch.empty(H, dtype=torch.float32, device=dev)
+            we = WGrad("wgrad_edge")
+            we.add(g0, e, dw0, db0)
+            we.run()
+            eg = [dw0, db0]
+            for l in range(3):
+                eg += [dW13[l], db13[l]]
+            eg = [t if t.dtype == p.dtype else t.to(p.dtype) for t, p in zip(eg, es.params()[:8])]
+            eg += list(_ln_grads(part_e, nb_e, H, es.ln[0].dtype))
+        else:
+            nb_e = bwd_nblocks(E)
+            part_e = torch.empty(nb_e, 2 * H, dtype=torch.float32, device=dev)
+            gpre_e = _alloc_gpre(es, E, dt, dev)
+            nb_e = mlp_backward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H, in_dim=H,
+                                wtpk=es.wtpk(), acts=ea, g=ge, g2=dagg, gidx=lv.dst, gpre=gpre_e, ln_g=es.lnp()[0],
+                                hpre=ehp, stats=est, din=[(H, de, True)], ln_partial=part_e, tag="edge_bwd",
+                                cost=with_alg(alg8d_edge(E, 0, H, sz, bwd=True), cost_edge_bwd(E, N, H, sz, es.nlin)))
+            eg = _chain_param_grads(es, gpre_e, e, ea, part_e, nb_e, tag="wgrad_edge")
+        grads_node = _chain_param_grads(ns, gpre_n, [x, agg], na, part_n, nb_n, tag="wgrad_node")
+        return (dx, de, None, None, None, *eg, *grads_node)
 
 
 # --------------------------------------------------------------------------- pooling

@@ -39,6 +39,14 @@
 // the dst of the rows next to the run's ends to tell) and zeros for the empty receivers at a row of
 // its run (those past the last edge: the wave with the last tile); a receiver that crosses the end of
 // a run is summed from e' by edge_agg_fixup_kernel, which recomputes the runs from (rows, grid).
+// Receiver means (MEAN, agn_edge_fwd_args.agg_mean): the same sums divided by (float)max(deg, 1) before
+// their one rounding, by the kernel and by the fix-up: bitwise agn_segment_sum(out, mean = 1).
+//
+// The projection-free chain (PROJ = false, agn_edge_fwd_args.proj == NULL):
+//   e' = e + LN(W3 relu(W2 relu(W1 relu(e W0^T + b0) + b1) + b2) + b3)
+// (models/trial1.py:61-65 MeshGraphNetLayer_v2), the same kernel with the accumulators started from b0
+// instead of the row sum; see the template's comment. DESIGN.md §7c has the register counts of every
+// instantiation (<= 168, none spills).
 #include <type_traits>
 #include "tile32.hpp"
 #include "aerognn.h"
@@ -72,6 +80,11 @@ struct SmemAgg : Smem {
   uint4 stage[NW][8 * 16];  // per wave: 8 rows of the rounded tile, chunk k of row r at [r][k ^ r]
 };
 static_assert(sizeof(SmemAgg) <= 160 * 1024, "LDS budget");
+template <class Base>
+struct SmemB0 : Base {
+  float pv0[H];  // the projection-free chain: b0, the bias of the first Linear
+};
+static_assert(sizeof(SmemB0<SmemAgg>) <= 160 * 1024, "LDS budget");
 typedef const __attribute__((address_space(4))) int32_t* cidx_t;  // index reads as scalar loads
 
 // Lin l's product: the resident kernel's per-accumulator sequence, fragments PF deep (tile32.hpp)
@@ -96,16 +109,28 @@ __device__ unsigned long long* agn_e32_stamps;
   } while (0)
 #endif
 
-template <bool SAVE, bool AGG>
+// PROJ = false: the projection-free chain e' = e + LN(W3 relu(W2 relu(W1 relu(e W0^T + b0) + b1) + b2) + b3)
+// (models/trial1.py MeshGraphNetLayer_v2's edge update): the accumulators start from b0 as the
+// resident kernel's do without projections (mlp.hip: the bias first, then the products), there are no
+// src ids and no P rows, and the dst ids are loaded only for the receiver aggregates.
+// MEAN (with AGG): a receiver's fp32 column sums are divided by (float)max(deg, 1), deg from rowptr,
+// before the one rounding (scatter_mean; segment_sum4_kernel's mean step).
+template <bool SAVE, bool AGG, bool PROJ = true, bool MEAN = false>
 __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_args a) {
+  static_assert(AGG || !MEAN, "means are receiver aggregates");
+  constexpr bool IDS = PROJ || AGG;  // the tile's node ids go through the wave's LDS slot
   constexpr int NTHR = 64 * NW;
-  __shared__ std::conditional_t<AGG, SmemAgg, Smem> sm;
+  using SmemT = std::conditional_t<AGG, SmemAgg, Smem>;
+  __shared__ std::conditional_t<PROJ, SmemT, SmemB0<SmemT>> sm;
   {
     const uint4* const* wp = reinterpret_cast<const uint4* const*>(a.wpk);
     for (int i = threadIdx.x; i < 4 * LAYER; i += NTHR) sm.w[i] = wp[i / LAYER][i % LAYER];
     for (int i = threadIdx.x; i < 5 * H; i += NTHR) {
       const int l = i / H, f = i - l * H;
       sm.pv[l][f] = l < 3 ? (a.bias[l + 1] ? a.bias[l + 1][f] : 0.f) : (l == 3 ? a.ln_g[f] : a.ln_b[f]);
+    }
+    if constexpr (!PROJ) {
+      for (int i = threadIdx.x; i < H; i += NTHR) sm.pv0[i] = a.bias[0] ? a.bias[0][i] : 0.f;
     }
   }
   __syncthreads();
@@ -114,9 +139,12 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
   const int ntiles = (a.rows + 31) / 32;
   const std::conditional_t<AGG, RangeWalk, Walk> walk(ntiles, w, NW);
   int* wids = sm.ids[w];
-  const int32_t* const idp = lane0 < 32 ? a.src : a.dst;
+  // (!PROJ: both lane halves load dst, so the slot's upper half holds it as with projections)
+  const int32_t* const idp = PROJ && lane0 < 32 ? a.src : a.dst;
   auto tile_id = [&](int t) { return idp[min(t * 32 + (lane0 & 31), a.rows - 1)]; };
-  if (walk.first < walk.end) wids[lane0] = tile_id(walk.first);
+  if constexpr (IDS) {
+    if (walk.first < walk.end) wids[lane0] = tile_id(walk.first);
+  }
   const bf16* P = reinterpret_cast<const bf16*>(a.proj);
   const bf16* E = reinterpret_cast<const bf16*>(a.e);
 #ifdef AGN_E32_STAMPS
@@ -132,6 +160,16 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
   auto agg_put = [&](int n, uint32_t v, int l) {
     if (AGN_E32_AGG_DIAG == 0 && (unsigned)n < (unsigned)a.nodes)
       *reinterpret_cast<uint32_t*>(aggp + (size_t)n * (2 * H) + (uint32_t)(4 * l)) = v;
+  };
+  // MEAN: receiver n's two column sums over its degree, rounded once (the sums' instantiations keep
+  // their statements as they were: routed through this helper their instruction stream moved)
+  auto mean2 = [&](int n, float s0, float s1) {
+    float cnt = 1.f;
+    if ((unsigned)n < (unsigned)a.nodes) {
+      const cidx_t ptr = (cidx_t)(uintptr_t)a.rowptr;
+      cnt = (float)max(ptr[n + 1] - ptr[n], 1);
+    }
+    return pack2(s0 / cnt, s1 / cnt);
   };
   uint32_t* park = nullptr;
   if constexpr (AGG && AGN_E32_AGG_DIAG != 1) {
@@ -151,10 +189,19 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
     const bool valid = row < a.rows;
     const int rr = valid ? row : a.rows - 1;
     const bool more = tile + walk.step < walk.end;
-    const int nid = tile_id(more ? tile + walk.step : tile);
+    int nid = 0;
+    if constexpr (IDS) nid = tile_id(more ? tile + walk.step : tile);
     f32x16 acc[NT];
     BOp<bf16, NR> b;
-    {
+    if constexpr (!PROJ) {
+      if constexpr (AGG) {
+        const int cd = wids[32 + c];
+        if constexpr (AGN_E32_AGG_DIAG != 1) park[c] = cd;
+        if (more) wids[lane] = nid;  // (this tile's reads of the slot are done: LDS is in order per wave)
+      }
+      b.load_w(E + (size_t)rr * H, h);
+      acc_bias(acc, sm.pv0, h);  // acc = b0: the resident kernel's start without projections
+    } else {
       const int cs = wids[c], cd = wids[32 + c];
       if constexpr (AGG && AGN_E32_AGG_DIAG != 1) park[c] = cd;
       if (more) wids[lane] = nid;  // (this tile's reads of the slot are done: LDS is in order per wave)
@@ -282,7 +329,11 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
             if ((lb >> r) & 1u) {
               if ((bb >> r) & 1u) {
                 const int d = __builtin_amdgcn_readlane(rcv, 8 * p + r);
-                if (!skip) agg_put(cur, pack2(s[0], s[1]), lane);
+                if constexpr (MEAN) {
+                  if (!skip) agg_put(cur, mean2(cur, s[0], s[1]), lane);
+                } else {
+                  if (!skip) agg_put(cur, pack2(s[0], s[1]), lane);
+                }
                 for (int n = cur + 1; n < d; ++n) agg_put(n, 0u, lane);  // the empty receivers at this row
                 cur = d;
                 skip = false;
@@ -305,7 +356,9 @@ __global__ __launch_bounds__(64 * NW) void edge32_fwd_kernel(const agn_edge_fwd_
   if constexpr (AGG && AGN_E32_AGG_DIAG != 1) {
     if (walk.first < walk.end) {
       cbarrier();
-      const uint32_t sum = pack2(__uint_as_float(park[64 + lane0]), __uint_as_float(park[128 + lane0]));
+      uint32_t sum;
+      if constexpr (MEAN) sum = skip ? 0u : mean2(cur, __uint_as_float(park[64 + lane0]), __uint_as_float(park[128 + lane0]));
+      else sum = pack2(__uint_as_float(park[64 + lane0]), __uint_as_float(park[128 + lane0]));
       const int rend = min(walk.end * 32, a.rows);
       if (rend == a.rows) {  // the last edge: its receiver ends here, the rest are empty
         if (!skip) agg_put(cur, sum, lane0);
@@ -348,6 +401,11 @@ __global__ __launch_bounds__(256) void edge_agg_fixup_kernel(const agn_edge_fwd_
         s1 += hi_bf16(v[q]);
       }
   }
+  if (a.agg_mean) {  // (a crossing receiver has edges: end > beg)
+    const float cnt = (float)max(end - beg, 1);
+    s0 = s0 / cnt;
+    s1 = s1 / cnt;
+  }
   *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.agg) + (size_t)n * (2 * H) + (uint32_t)(4 * lane)) = pack2(s0, s1);
 }
 
@@ -376,7 +434,11 @@ int agn_edge_forward32(const agn_edge_fwd_args* a, void* stream) {
       return launch_status();
     return 0;
   }
-  if (!a->e || !a->proj || !a->src || !a->dst || !a->out || !a->ln_g || !a->ln_b) return AGN_E_ARG;
+  // proj == NULL: the projection-free chain (no src; dst only for the receiver aggregates)
+  const bool proj = a->proj != nullptr;
+  if (!a->e || !a->out || !a->ln_g || !a->ln_b) return AGN_E_ARG;
+  if (proj ? (!a->src || !a->dst) : (a->agg && !a->dst)) return AGN_E_ARG;
+  if (a->agg_mean != 0 && (a->agg_mean != 1 || !a->agg)) return AGN_E_ARG;
   if (a->act[1] || a->act[2] || a->hpre) return AGN_E_ARG;  // a1 and the statistics are the only saves
   const bool save = a->act[0] != nullptr;
   if (save != (a->stats != nullptr) || (save && (!al16(a->act[0]) || (reinterpret_cast<uintptr_t>(a->stats) & 7))))
@@ -384,23 +446,36 @@ int agn_edge_forward32(const agn_edge_fwd_args* a, void* stream) {
   for (int l = 0; l < 4; ++l)
     if (!a->wpk[l] || !al16(a->wpk[l])) return AGN_E_ARG;
   if (!al16(a->e) || !al16(a->proj) || !al16(a->out)) return AGN_E_ARG;
+  if (!proj && a->bias[0] && (reinterpret_cast<uintptr_t>(a->bias[0]) & 3)) return AGN_E_ARG;
   if (a->agg && (!a->rowptr || a->nodes < 1 || !al16(a->agg))) return AGN_E_ARG;
   const dim3 g(a->nblk), blk(64 * NW);
   hipStream_t st = (hipStream_t)stream;
-  if (a->agg) {
-    ++g_agg_launches;
-    if (save) hipLaunchKernelGGL((edge32_fwd_kernel<true, true>), g, blk, 0, st, *a);
-    else hipLaunchKernelGGL((edge32_fwd_kernel<false, true>), g, blk, 0, st, *a);
+  if (a->agg) ++g_agg_launches;
+  // (SAVE, AGG, PROJ, MEAN) -> the instantiation; the sum-trick ones with sums are the four of before
+#define E32_LAUNCH(S, A, P, M) hipLaunchKernelGGL((edge32_fwd_kernel<S, A, P, M>), g, blk, 0, st, *a)
+#define E32_BY_SAVE(A, P, M)     \
+  do {                           \
+    if (save) E32_LAUNCH(true, A, P, M); \
+    else E32_LAUNCH(false, A, P, M);     \
+  } while (0)
+  if (proj) {
+    if (!a->agg) E32_BY_SAVE(false, true, false);
+    else if (!a->agg_mean) E32_BY_SAVE(true, true, false);
+    else E32_BY_SAVE(true, true, true);
   } else {
-    if (save) hipLaunchKernelGGL((edge32_fwd_kernel<true, false>), g, blk, 0, st, *a);
-    else hipLaunchKernelGGL((edge32_fwd_kernel<false, false>), g, blk, 0, st, *a);
+    if (!a->agg) E32_BY_SAVE(false, false, false);
+    else if (!a->agg_mean) E32_BY_SAVE(true, false, false);
+    else E32_BY_SAVE(true, false, true);
   }
+#undef E32_BY_SAVE
+#undef E32_LAUNCH
   return launch_status();
 }
 
 int agn_edge_agg_fixup(const agn_edge_fwd_args* a, void* stream) {
   if (!a || a->rows < 0 || a->nblk < 1 || a->nblk > (1 << 20)) return AGN_E_ARG;
   if (!a->agg || !a->rowptr || a->nodes < 1 || !al16(a->agg)) return AGN_E_ARG;
+  if (a->agg_mean != 0 && a->agg_mean != 1) return AGN_E_ARG;
   if (a->rows == 0) return 0;
   if (!a->dst || !a->out || !al16(a->out)) return AGN_E_ARG;
   hipLaunchKernelGGL(edge_agg_fixup_kernel, dim3((a->nblk * NW + 3) / 4), dim3(256), 0, (hipStream_t)stream, *a);

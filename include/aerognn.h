@@ -445,18 +445,20 @@ int agn_fault_status_async(int* host_pinned, void* stream);
 /* testing: sets the fault word (as a ring wait that gave up would), so the host-side polling can be
  * exercised without a real fault */
 int agn_debug_set_fault(int value);
-/* ---- arguments of the sum-trick edge chain's forward kernel (agn_edge_forward32) ---- */
+/* ---- arguments of the edge chain's forward kernel (agn_edge_forward32): the sum-trick chain, or
+ * with proj == NULL the projection-free chain of models/trial1.py ---- */
 typedef struct {
   int rows;                  /* edges (CSC order) */
   int nblk;                  /* grid size: agn_edge_fwd32_blocks(rows) */
   const void* wpk[4];        /* packed A = W_l of W_e, Lin1, Lin2, Lin3 (agn_pack trans = 0, bf16) */
-  const float* bias[4];      /* fp32 biases; bias[1..3] of Lin1..Lin3 (bias[0] unused) */
+  const float* bias[4];      /* fp32 biases; bias[1..3] of Lin1..Lin3; bias[0] = b0 of the projection-free chain
+                              * (NULL = none), unused by the sum-trick chain */
   const float* ln_g;         /* LayerNorm gamma, beta [128] */
   const float* ln_b;
   const void* e;             /* [rows][128] edge input = the residual */
-  const void* proj;          /* [N][256] P = [x W_s^T | x W_d^T + b] */
-  const int32_t* src;
-  const int32_t* dst;
+  const void* proj;          /* [N][256] P = [x W_s^T | x W_d^T + b]; NULL = the projection-free chain */
+  const int32_t* src;        /* (unused without proj) */
+  const int32_t* dst;        /* (without proj: read only when agg is set) */
   void* out;                 /* [rows][128] e' */
   void* act[3];              /* training saves: act[0] = a1 in AGN_TILED (rows padded to 32); act[1..2] NULL */
   void* hpre;                /* must be NULL */
@@ -465,7 +467,8 @@ typedef struct {
   void* agg;                 /* [nodes][128]: agg[n] = sum of out's rows rowptr[n] .. rowptr[n+1]-1 */
   const int32_t* rowptr;     /* [nodes + 1] CSC row pointer of dst (rows grouped by receiver, ascending) */
   int nodes;
-  int _pad;
+  int agg_mean;              /* 0 = sums (scatter_add), 1 = means: each sum / (float)max(deg, 1) before its one
+                              * rounding (scatter_mean); 1 needs agg */
 } agn_edge_fwd_args;
 /* The chain on 32-edge tiles with 32x32x16 MFMAs, bitwise agn_mlp_forward's resident kernel
  * on the same operands: the forward of the training step (fused backward) and of inference.
@@ -479,7 +482,13 @@ typedef struct {
  * order with one rounding, and zeros for the empty receivers; agg need not be initialised. A
  * receiver whose range crosses the end of a run is left to agn_edge_agg_fixup, which must follow on
  * the same stream with the same arguments: it sums those (at most one per wave of the grid) from
- * out. After both, agg is bitwise agn_segment_sum(out). */
+ * out. After both, agg is bitwise agn_segment_sum(out), with agg_mean = 1 agn_segment_sum(out, mean = 1).
+ * With proj == NULL the chain is the projection-free e' = e + LN(W3 relu(W2 relu(W1 relu(e W0^T + b0)
+ * + b1) + b2) + b3) of MeshGraphNetLayer_v2 (models/trial1.py:61-65): the accumulators start from
+ * bias[0] instead of P_s[src] + P_d[dst], src is not read and dst only for agg; everything after
+ * layer 0, the saves included, is the same, and the result is bitwise agn_mlp_forward's resident
+ * kernel on one plain segment with bias[0] = b0 and resid = e. agn_edge_bwd_fused on its saves
+ * (a1, stats) is that chain's backward from Lin1 on; dW0 = G0^T e and db0 go to agn_wgrad. */
 int agn_edge_fwd32_blocks(int rows);
 int agn_edge_forward32(const agn_edge_fwd_args* a, void* stream);
 int agn_edge_agg_fixup(const agn_edge_fwd_args* a, void* stream);
