@@ -131,7 +131,8 @@ LAUNCHES = ("agn_pack", "agn_mlp_forward", "agn_mlp_backward", "agn_reduce_parti
             "agn_wec_backward", "agn_edge_features", "agn_node_features", "agn_normalize", "agn_col_stats", "agn_collate",
             "agn_segment_max", "agn_segment_max_backward", "agn_edge_bwd_fused", "agn_encoder_bwd_fused", "agn_wgrad_reduce",
             "agn_edge_forward32", "agn_edge_agg_fixup",
-            "agn_proj_forward", "agn_proj_backward", "agn_fourier_embed", "agn_fourier_embed_bwd")
+            "agn_proj_forward", "agn_proj_backward", "agn_fourier_embed", "agn_fourier_embed_bwd", "agn_eval_sums",
+            "agn_aero_forces")
 
 
 class AeroGNNError(RuntimeError):
@@ -251,6 +252,12 @@ def lib():
             "agn_wec_backward": (i32, [C.POINTER(WecArgs), vp]),
             "agn_fourier_embed": (i32, [i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
             "agn_fourier_embed_bwd": (i32, [i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp]),
+            "agn_aero_chunk_rows": (i32, []),
+            "agn_eval_sums_temp_bytes": (C.c_size_t, [i32, i32, i32]),
+            "agn_eval_sums": (i32, [i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
+            "agn_aero_forces_temp_bytes": (C.c_size_t, [i32, i32]),
+            "agn_aero_forces": (i32, [i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, C.c_int64, vp, vp,
+                                      C.c_double, vp, C.POINTER(C.c_double), vp, i32, vp, vp, vp]),
             "agn_f64_gemm": (i32, [C.POINTER(F64GemmArgs), vp]),
             "agn_f64_wgrad_scratch_bytes": (C.c_size_t, [C.POINTER(F64WgradArgs)]),
             "agn_f64_wgrad": (i32, [C.POINTER(F64WgradArgs), vp, vp]),

@@ -25,6 +25,13 @@ torch.compile / FakeTensorMode, and autograd formulas that are themselves torch.
       [x | cos(f_i x_j), sin(f_i x_j)] of the first d columns, f_i = 2^(freq_start + i) pi
       (fouriermgn.py:111-151, :167-170): agn_fourier_embed. Backward: fourier_embed_backward
       (agn_fourier_embed_bwd, the trig recomputed from x).
+  eval_sums(pred [n,f], y [n,f], mean [f], std [f], gptr int32 [G+1]) -> float64 [G, 2, f, 6]
+      per graph, scale (normalised, physical) and feature: sum |d|, sum d^2, sum |t|, count of
+      |t| > 1e-8, sum |d/t|, sum (d/t)^2 (inference.py:76-126, :337-350, :395-413): agn_eval_sums.
+  aero_forces(pressure [n], shear [n,dim], normals [n,dim], pos?, areas?, edge_index?, gptr, center,
+              length_scale=1e-2) -> (float64 [G, 4, 3] = sum F, sum M, sum |F|, sum |M|; areas float64 [n])
+      surface integration of utils.py:385-448 / :451-559 with either the given element areas or
+      the node areas of utils.py:510-520 from the mesh: agn_aero_forces. No autograd (evaluation).
 
 The fused MLP / MeshGraphNet-layer kernels are not registered as operators: their calls carry
 packed-weight caches and a per-level CSC plan (Python objects), so they stay
@@ -279,6 +286,125 @@ def _fourier_bwd(ctx, g):
 
 
 torch.library.register_autograd("aerognn::fourier_embed", _fourier_bwd, setup_context=_fourier_ctx)
+
+
+# ------------------------------------------------------------------------------- evaluation
+def _wide(t: Tensor, dtype=None) -> Tensor:
+    """bf16 / fp16 widened to fp32 (exact); fp32 / fp64 kept; `dtype` forces the compute type."""
+    if dtype is not None:
+        return t if t.dtype == dtype else t.to(dtype)
+    if t.dtype in (torch.float32, torch.float64):
+        return t
+    if t.dtype in (torch.bfloat16, torch.float16):
+        return t.float()
+    raise TypeError(f"aerognn evaluation ops take floating-point tensors, got {t.dtype}")
+
+
+def _check_gptr(gptr: Tensor, what: str) -> Tensor:
+    if gptr.dim() != 1 or gptr.numel() < 1 or gptr.dtype != I32:
+        raise ValueError(f"{what}: gptr must be an int32 vector of ngraph + 1 row offsets")
+    return gptr.contiguous()
+
+
+@torch.library.custom_op("aerognn::eval_sums", mutates_args=())
+def eval_sums(pred: Tensor, y: Tensor, mean: Tensor, std: Tensor, gptr: Tensor) -> Tensor:
+    from ._lib import check, lib, ptr
+    from .core import dt_code, stream
+    require_device(pred, y, mean, std, gptr)
+    if pred.dim() != 2 or y.shape != pred.shape:
+        raise ValueError("eval_sums: pred and y must be 2-D [rows, features] tensors of one shape")
+    n, f = pred.shape
+    if mean.numel() != f or std.numel() != f:
+        raise ValueError("eval_sums: mean and std must have one entry per feature")
+    pred = _embed_rows(_wide(pred), "eval_sums")
+    dt = pred.dtype
+    y = _embed_rows(_wide(y, dt), "eval_sums")
+    mean = _wide(mean, dt).reshape(-1).contiguous()
+    std = _wide(std, dt).reshape(-1).contiguous()
+    gptr = _check_gptr(gptr, "eval_sums")
+    G = gptr.numel() - 1
+    if n == 0 or G == 0:  # no launch: empty graphs give zeros
+        return torch.zeros(G, 2, f, 6, dtype=torch.float64, device=pred.device)
+    out = torch.empty(G, 2, f, 6, dtype=torch.float64, device=pred.device)  # the finishing pass writes every entry
+    nb = int(lib().agn_eval_sums_temp_bytes(n, f, G))
+    if nb == 0:
+        raise ValueError(f"eval_sums: {f} features (the kernel takes 1..16)")
+    scratch = torch.empty(nb, dtype=torch.uint8, device=pred.device)
+    check(lib().agn_eval_sums(dt_code(dt), n, f, ptr(pred), pred.stride(0), ptr(y), y.stride(0), ptr(mean), ptr(std),
+                              ptr(gptr), G, ptr(out), ptr(scratch), stream()), "eval_sums")
+    return out
+
+
+@eval_sums.register_fake
+def _(pred, y, mean, std, gptr):
+    return pred.new_empty(gptr.shape[0] - 1, 2, pred.shape[1], 6, dtype=torch.float64)
+
+
+@torch.library.custom_op("aerognn::aero_forces", mutates_args=())
+def aero_forces(pressure: Tensor, shear: Tensor, normals: Tensor, pos: Optional[Tensor], areas: Optional[Tensor],
+                edge_index: Optional[Tensor], gptr: Tensor, center: list[float],
+                length_scale: float = 1e-2) -> tuple[Tensor, Tensor]:
+    """(sums [G, 4, 3] float64 = sum F, sum M, sum |F|, sum |M|; areas float64 [n] of the mesh rule, or
+    [0] when the areas were given)."""
+    import ctypes as C
+    from ._lib import check, lib, ptr
+    from .core import dt_code, stream
+    from .graph import group_by
+    require_device(pressure, shear, normals, pos, areas, edge_index, gptr)
+    if shear.dim() != 2 or shear.shape[1] not in (2, 3):
+        raise ValueError("aero_forces: shear must be [n, 2] or [n, 3]")
+    n, dim = shear.shape
+    if normals.shape != shear.shape or pressure.numel() != n or (pos is not None and pos.shape != shear.shape):
+        raise ValueError("aero_forces: pressure [n], shear, normals and pos [n, dim] must agree")
+    if (areas is None) == (edge_index is None):
+        raise ValueError("aero_forces: give either the element areas or the mesh (edge_index), not both")
+    if edge_index is not None and pos is None:
+        raise ValueError("aero_forces: the mesh rule for the areas needs pos")
+    if len(center) not in (0, dim):
+        raise ValueError("aero_forces: center must have one entry per dimension")
+    pressure = _wide(pressure).reshape(-1).contiguous()
+    dt = pressure.dtype
+    shear = _embed_rows(_wide(shear, dt), "aero_forces")
+    normals = _embed_rows(_wide(normals, dt), "aero_forces")
+    pos = None if pos is None else _embed_rows(_wide(pos, dt), "aero_forces")
+    gptr = _check_gptr(gptr, "aero_forces")
+    G = gptr.numel() - 1
+    dev = pressure.device
+    # the finishing pass writes every entry; without a launch (n == 0) empty graphs give zeros
+    out = (torch.empty if n and G else torch.zeros)(G, 4, 3, dtype=torch.float64, device=dev)
+    rowptr = perm = ei = None
+    e = 0
+    if edge_index is not None:
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+            raise ValueError("aero_forces: edge_index must be [2, E]")
+        ei = edge_index.to(torch.int64).contiguous()
+        e = ei.shape[1]
+        if e and (int(ei.min()) < 0 or int(ei.max()) >= n):
+            raise IndexError(f"aero_forces: edge_index out of range [0, {n})")
+        perm, rowptr = group_by(ei[0], n)  # stable: a node's outgoing edges stay in the caller's order
+        area_out = torch.zeros(n, dtype=torch.float64, device=dev)
+    else:
+        areas = areas.to(torch.float64).reshape(-1).contiguous()
+        if areas.numel() != n:
+            raise ValueError("aero_forces: areas must have one entry per element")
+        area_out = torch.empty(0, dtype=torch.float64, device=dev)
+    if n == 0 or G == 0:
+        return out, area_out
+    ctr = (C.c_double * dim)(*[float(c) for c in center]) if len(center) else None
+    scratch = torch.empty(int(lib().agn_aero_forces_temp_bytes(n, G)), dtype=torch.uint8, device=dev)
+    check(lib().agn_aero_forces(dt_code(dt), n, dim, ptr(pressure), ptr(shear), shear.stride(0), ptr(normals),
+                                normals.stride(0), ptr(pos), 0 if pos is None else pos.stride(0), ptr(areas),
+                                ptr(ei), e, ptr(rowptr), ptr(perm), float(length_scale),
+                                ptr(area_out) if ei is not None else None, ctr, ptr(gptr), G, ptr(out), ptr(scratch),
+                                stream()), "aero_forces")
+    return out, area_out
+
+
+@aero_forces.register_fake
+def _(pressure, shear, normals, pos, areas, edge_index, gptr, center, length_scale=1e-2):
+    n = shear.shape[0] if edge_index is not None else 0
+    return (shear.new_empty(gptr.shape[0] - 1, 4, 3, dtype=torch.float64),
+            shear.new_empty(n, dtype=torch.float64))
 
 
 # ------------------------------------------------------------------------------- PyG-style pools

@@ -551,6 +551,51 @@ int agn_fourier_embed(int dtype, int n, int k, const void* x, int ld, int d, int
 int agn_fourier_embed_bwd(int dtype, int n, int k, const void* x, int ld, int d, int freq_start, int freq_len,
                           int with_input, const void* g, int g_ld, void* dx, int dx_ld, void* stream);
 
+/* ---- evaluation on the device: error metrics and aerodynamic coefficients.
+ * Replaces (reference file:line): inference.py:76-126 (de-normalisation, compute_errors,
+ * compute_rrmse_percent), :337-350 (per-case feature errors), :395-413 (test-set means);
+ * utils.py:385-448 (calculate_aero_coefficients_3d), :451-559 (calculate_aero_coefficients_2d, with
+ * the per-edge Python loop of :510-520).
+ * Both entries reduce in fp64 in two stages with fixed tree shapes and no atomics: per-chunk partials
+ * (agn_aero_chunk_rows() rows per chunk, chunks laid out from each graph's first row), then one pass
+ * that adds a graph's partials in ascending chunk order. The result for graph g of a batch is bitwise
+ * the result of evaluating graph g alone, and two calls give identical bytes.
+ * gptr: int32 [ngraph + 1], the row range of each graph (ascending; ranges are clamped to [0, n]).
+ *
+ * agn_eval_sums: pred, y [n][f] (row strides pred_ld, y_ld), mean, std [f], all of dtype AGN_F32 or
+ *   AGN_F64. out [ngraph][2][f][6] doubles; scale 0 = normalised (p = pred, t = y), scale 1 = physical
+ *   (p = pred * std rounded, + mean rounded; t likewise from y: never an FMA). Per feature, with
+ *   d = p - t rounded once in the input dtype and d / t a correctly rounded division in that dtype:
+ *     [0] sum |d|   [1] sum d^2   [2] sum |t|   [3] count of |t| > 1e-8
+ *     [4] sum |d / t| and [5] sum (d / t)^2 over the rows counted in [3]
+ *   the squares and all sums in fp64. Empty graphs give zeros.
+ * agn_aero_forces: n elements (2-D nodes or 3-D cells), dim in {2, 3}; pressure [n], shear and normals
+ *   [n][dim] (row strides), pos [n][dim] or NULL (no moments; required with a mesh), dtype AGN_F32 or
+ *   AGN_F64. Element areas are either given (areas, double [n]) or the 2-D rule of utils.py:510-520
+ *   from the mesh (edge_index int64 [2][e]; rowptr int32 [n + 1] and perm int32 [e], a STABLE grouping of
+ *   the edges by sender edge_index[0]):
+ *     area[v] = sum over edges i with sender v, ascending i, of |pos[dst_i] - pos[v]| * (0.5 * length_scale)
+ *   coordinate differences in the input dtype, norm, scaling and sum in fp64 (the reference's
+ *   length_scale is 1e-2); stored to area_out (double [n]) when not NULL. Per element
+ *     pn = pressure * normal (rounded once in the input dtype); F = pn * area - shear * area (fp64)
+ *     r = pos - center (fp64; center: host double [dim], NULL = origin, copied at the call)
+ *     2-D: M = r_x F_y - r_y F_x;   3-D: M = r x F
+ *   out [ngraph][4][3] doubles: sum F, sum M, sum |F|, sum |M| per component (2-D: F = (Fx, Fy, 0),
+ *   M = (Mz, 0, 0)); the absolute sums are the scale an error of the signed sums is judged against.
+ * scratch: agn_*_temp_bytes(...) bytes, 16-B aligned. Errors: AGN_E_ARG (null pointer, negative count),
+ * AGN_E_DTYPE, AGN_E_SHAPE (f outside 1..16, dim outside {2, 3}, a row stride narrower than the row,
+ * areas and mesh both given or both missing). n == 0 returns 0 without a launch. */
+int agn_aero_chunk_rows(void);
+size_t agn_eval_sums_temp_bytes(int n, int f, int ngraph);
+int agn_eval_sums(int dtype, int n, int f, const void* pred, int pred_ld, const void* y, int y_ld, const void* mean,
+                  const void* std, const int32_t* gptr, int ngraph, double* out, void* scratch, void* stream);
+size_t agn_aero_forces_temp_bytes(int n, int ngraph);
+int agn_aero_forces(int dtype, int n, int dim, const void* pressure, const void* shear, int shear_ld,
+                    const void* normals, int normals_ld, const void* pos, int pos_ld, const double* areas,
+                    const int64_t* edge_index, int64_t e, const int32_t* rowptr, const int32_t* perm,
+                    double length_scale, double* area_out, const double* center, const int32_t* gptr, int ngraph,
+                    double* out, void* scratch, void* stream);
+
 /* ---- float64 mode (train.py:20-40 precision "double" / "float64"): the MLP / GMP path in fp64
  * on plain LDS-tiled FMA kernels (csrc/f64.hip); graph ops take dtype AGN_F64. */
 typedef struct {
