@@ -175,26 +175,31 @@ def _chain_param_grads(spec, gpre, inputs0, acts, lnp_partial, nblk, wg=None, ta
 
 
 # --------------------------------------------------------------------------- MLP
-def _ksegs(x, H):
-    """Split an input row of K features into segments of <= H (multiples of 32 but the last)."""
+def _kblocks(x, H):
+    """Column blocks (k0, k) of an input row of K features, each <= H wide (H but the last)."""
     K = x.shape[1]
-    segs, k0 = [], 0
-    while k0 < K:
-        k = min(H, K - k0)
-        segs.append((k0, k))
-        k0 += k
-    return segs
+    return [(k0, min(H, K - k0)) for k0 in range(0, K, H)]
+
+
+def _ksegs(x, H):
+    """Input segments (k0, k) of a row of K features: up to AGN_MAX_SEG segments of <= H columns
+    (multiples of 32 but the last), or, past 3 H, one wide segment that the kernels walk in H-wide
+    column blocks themselves (agn_seg in aerognn.h): the same products in the same order."""
+    blocks = _kblocks(x, H)
+    return blocks if len(blocks) <= L.MAX_SEG else [(0, x.shape[1])]
 
 
 class MLPFn(torch.autograd.Function):
     """models/mlp.py:40-51. `rows` (int64 / int32 [R] or None): the chain runs on x[rows] with the
     gather done by the kernel's input loads (SEG_GATHER); the input gradient is then scattered
-    back with a fixed-order segment sum over the rows that read each input row."""
+    back with a fixed-order segment sum over the rows that read each input row. The input may be
+    any width: see _ksegs."""
 
     @staticmethod
     def forward(ctx, x, spec: ChainSpec, train, rows, *params):
         require_device(x)
-        x = _c(x)
+        # (a wide input, e.g. a column slice of a wider tensor, is read through its row stride)
+        x = _c(x) if x.shape[1] <= L.MAX_SEG * spec.hidden else _rows_ld(x)
         nrow = x.shape[0] if rows is None else rows.numel()
         dt = x.dtype
         out = torch.empty(nrow, spec.out_dim, dtype=dt, device=x.device)
@@ -202,8 +207,6 @@ class MLPFn(torch.autograd.Function):
         fused = train and _core.encoder_fused_ok(spec, dt, x.shape[1], nrow, ctx.needs_input_grad[0])
         acts, hpre, stats = _alloc_saves(spec, nrow, dt, x.device, train and not fused)
         ks = _ksegs(x, spec.hidden)
-        if len(ks) > L.MAX_SEG:
-            raise NotImplementedError("aerognn MLP input wider than 3 x hidden")
         idx = None
         if rows is not None:
             idx = rows.to(torch.int32).contiguous()
@@ -270,6 +273,10 @@ class MLPFn(torch.autograd.Function):
                 segment_sum(x.shape[0], x.shape[1], rp, perm, dx, dxs)
                 dx = dxs
         x0 = x if ctx.idx is None else [(x, ctx.idx)]  # the gathered rows, read through agn_wgrad's xidx
+        if len(ks) == 1 and ks[0][1] > spec.hidden:
+            # a wide input: dW0 in H-wide column blocks, each reading its slice of x through the row stride
+            x0 = [x[:, k0:k0 + k] if ctx.idx is None else (x[:, k0:k0 + k], ctx.idx)
+                  for k0, k in _kblocks(x, spec.hidden)]
         grads = _chain_param_grads(spec, gpre, x0, ctx.acts, part, nblk)
         return (dx, None, None, None, *grads)
 

@@ -142,13 +142,24 @@ AGN_DEV void load_segment(float (&in)[NR], const agn_seg& s, int rr, bool valid,
   }
 }
 
+// Columns [c0, c0 + kb) of a PLAIN / GATHER segment wider than the hidden size (kb <= NR * 2
+// features, masked: neither c0 nor the row stride need keep the row 16-B aligned).
+template <typename T, int NR>
+AGN_DEV void load_segment_block(float (&in)[NR], const agn_seg& s, int rr, int h, int c0, int kb) {
+  const int r = (s.kind == AGN_SEG_GATHER) ? s.index[rr] : rr;
+  load_row<T, NR, false>(in, reinterpret_cast<const T*>(s.ptr) + (size_t)r * s.ld + c0, kb, h);
+}
+
 // ------------------------------------------------------------------------- forward
 // I/O modes of the general kernels (compile-time, chosen on the host per call):
 //   M_VEC : every input segment and the output are H wide (16-B row I/O everywhere)
 //   M_NIN : one PLAIN or GATHER input of k <= 16 features (encoders: d_n = 6, d_e = 4), output H wide
 //   M_NOUT: H-wide inputs, nlin > 1, output of <= 32 features, no LayerNorm (decoder: d_out = 4)
 //   M_GEN : anything else (masked 4-feature chunks)
-enum { M_VEC = 0, M_GEN = 1, M_NIN = 2, M_NOUT = 3 };
+// M_WIDE (host-side only) selects the WIDE instantiations of M_GEN: a PLAIN / GATHER input segment
+// (forward) or a dX segment (backward) wider than H, walked in H-wide column blocks. They are
+// instantiations of their own so that the code of every other shape stays what it was.
+enum { M_VEC = 0, M_GEN = 1, M_NIN = 2, M_NOUT = 3, M_WIDE = 4 };
 
 // k <= 16 features of one row into acc-layout registers (features >= k and >= 16 are zero)
 template <typename T, int NR>
@@ -229,8 +240,9 @@ AGN_DEV void set_act(BOp<T, NR>& b, const f32x16 (&acc)[NT], int k, T* pre, int 
 
 // GACT: a hidden activation other than ReLU (agn_mlp_*_args.act_fn); the ReLU instantiations
 // carry none of its registers
-template <typename T, int NT, int MODE, bool GACT>
+template <typename T, int NT, int MODE, bool GACT, bool WIDE = false>
 __global__ __launch_bounds__(BLOCK, 2) void mlp_fwd_kernel(const agn_mlp_fwd_args a) {
+  static_assert(!WIDE || MODE == M_GEN, "wide segments run on the masked-I/O mode");
   constexpr int H = 32 * NT;
   constexpr int NR = 16 * NT;
   constexpr int NUH = nrk(H) / BOp<T, NR>::RPU;  // K units of an H-wide input
@@ -292,40 +304,46 @@ __global__ __launch_bounds__(BLOCK, 2) void mlp_fwd_kernel(const agn_mlp_fwd_arg
     } else {
       acc_bias<NT, OUT_FULL || MODE == M_NOUT>(acc, a.bias[0] ? a.bias[0] + gofs : nullptr, nv0, h);
     }
-    // ---- layer 0: sum over input segments
+    // ---- layer 0: sum over input segments. WIDE: a PLAIN / GATHER segment wider than H is walked
+    // in H-wide column blocks (the last may be narrow), one stage_block of W0 per block: the
+    // products and their order are those of consecutive H-wide segments
     int unit = 0;
     for (int s = 0; s < a.nseg; ++s) {
-      const int nu = units_k<T>(a.seg[s].k);
-      __syncthreads();
-      stage_block(wl, a.wpk[0], ku0, grp * NT, otn0, unit, nu);
-      if constexpr (MODE == M_NIN) {  // PLAIN, or GATHER (the caller's row order permuted in the load)
-        const int src_row = a.seg[s].kind == AGN_SEG_GATHER ? a.seg[s].index[rr] : rr;
-        load_row_narrow<T, NR>(v, reinterpret_cast<const T*>(a.seg[s].ptr) + (size_t)src_row * a.seg[s].ld, a.seg[s].k, h);
-      } else {
-        bool staged = false;
-        if constexpr (STAGE && IN_FULL) {
-          if (a.seg[s].kind == AGN_SEG_PLAIN) {
-            uint4 mine[NR / 8];
-            tile_load_chunks<4 * NT>(mine, reinterpret_cast<const bf16*>(a.seg[s].ptr) + (size_t)wave * 32 * a.seg[s].ld,
-                                     a.rows - wave * 32, stg[threadIdx.x >> 6], lane, a.seg[s].ld / 8);
-            b.set_w(mine);  // the operand from the chunks directly (no fp32 round trip)
-            staged = true;
+      for (int c0 = 0; c0 < (WIDE ? a.seg[s].k : 1); c0 += H) {
+        const int kb = WIDE ? min(H, a.seg[s].k - c0) : a.seg[s].k;
+        const int nu = units_k<T>(kb);
+        __syncthreads();
+        stage_block(wl, a.wpk[0], ku0, grp * NT, otn0, unit, nu);
+        if constexpr (MODE == M_NIN) {  // PLAIN, or GATHER (the caller's row order permuted in the load)
+          const int src_row = a.seg[s].kind == AGN_SEG_GATHER ? a.seg[s].index[rr] : rr;
+          load_row_narrow<T, NR>(v, reinterpret_cast<const T*>(a.seg[s].ptr) + (size_t)src_row * a.seg[s].ld, a.seg[s].k, h);
+        } else {
+          bool staged = false;
+          if constexpr (STAGE && IN_FULL) {
+            if (a.seg[s].kind == AGN_SEG_PLAIN) {
+              uint4 mine[NR / 8];
+              tile_load_chunks<4 * NT>(mine, reinterpret_cast<const bf16*>(a.seg[s].ptr) + (size_t)wave * 32 * a.seg[s].ld,
+                                       a.rows - wave * 32, stg[threadIdx.x >> 6], lane, a.seg[s].ld / 8);
+              b.set_w(mine);  // the operand from the chunks directly (no fp32 round trip)
+              staged = true;
+            }
+          }
+          if (!staged) {
+            if (W2 && walk2 && s == 1) staged = true;
+            else if (WIDE && a.seg[s].k > H) load_segment_block<T, NR>(v, a.seg[s], rr, h, c0, kb);
+            else load_segment<T, NR, IN_FULL>(v, a.seg[s], rr, valid, h);
           }
         }
-        if (!staged) {
-          if (W2 && walk2 && s == 1) staged = true;
-          else load_segment<T, NR, IN_FULL>(v, a.seg[s], rr, valid, h);
-        }
+        bool staged_b = false;
+        if constexpr (STAGE && IN_FULL && MODE != M_NIN) staged_b = a.seg[s].kind == AGN_SEG_PLAIN;
+        if (W2 && walk2 && s == 1) b = bagg;
+        else if (!staged_b) b.set(v);
+        __syncthreads();
+        if constexpr (IN_FULL) gemm<T, NT, NR, true>(acc, b, NUH, wl, NUH, NT, lane);
+        else if constexpr (MODE == M_NIN) gemm<T, NT, NR, true>(acc, b, nu, wl, nu, NT, lane);
+        else gemm<T, NT, NR>(acc, b, nu, wl, nu, otn0, lane);
+        unit += nu;
       }
-      bool staged_b = false;
-      if constexpr (STAGE && IN_FULL && MODE != M_NIN) staged_b = a.seg[s].kind == AGN_SEG_PLAIN;
-      if (W2 && walk2 && s == 1) b = bagg;
-      else if (!staged_b) b.set(v);
-      __syncthreads();
-      if constexpr (IN_FULL) gemm<T, NT, NR, true>(acc, b, NUH, wl, NUH, NT, lane);
-      else if constexpr (MODE == M_NIN) gemm<T, NT, NR, true>(acc, b, nu, wl, nu, NT, lane);
-      else gemm<T, NT, NR>(acc, b, nu, wl, nu, otn0, lane);
-      unit += nu;
     }
     // ---- hidden layers: relu(acc) -> packed operand -> next Linear (registers only)
     for (int l = 1; l < a.nlin; ++l) {
@@ -472,8 +490,9 @@ AGN_DEV void load_grad(float (&g)[NR], const agn_mlp_bwd_args& a, int rr, bool v
 
 // GACT: a hidden activation other than ReLU (agn_mlp_*_args.act_fn); the ReLU instantiations
 // carry none of its registers
-template <typename T, int NT, int MODE, bool GACT>
+template <typename T, int NT, int MODE, bool GACT, bool WIDE = false>
 __global__ __launch_bounds__(BLOCK, 2) void mlp_bwd_kernel(const agn_mlp_bwd_args a) {
+  static_assert(!WIDE || MODE == M_GEN, "wide segments run on the masked-I/O mode");
   constexpr bool VEC = (MODE == M_VEC);
   constexpr int H = 32 * NT;
   constexpr int NR = 16 * NT;
@@ -600,7 +619,24 @@ __global__ __launch_bounds__(BLOCK, 2) void mlp_bwd_kernel(const agn_mlp_bwd_arg
       int koff = 0;
       for (int s = 0; s < a.din_nseg; ++s) {
         const int ks = a.din_k[s];
-        if (a.din[s]) {
+        if (WIDE && a.din[s] && ks > H) {
+          // a segment wider than H (no residual form): dX[:, blk] = dh0 . W0[:, blk] per H-wide
+          // column block from the packed W0^T, written straight into the one [rows][ks] buffer
+          // (row stride ks: the rows need not be 16-B aligned, so the stores are masked)
+          for (int c0 = 0; c0 < ks; c0 += H) {
+            const int kb = min(H, ks - c0);
+            const int otn = (kb + 31) / 32;
+            __syncthreads();
+            stage_block(wl, a.wtpk[0], kuM, (koff + c0) / 32, otn, 0, kuM);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = f32x16{};
+            __syncthreads();
+            gemm<T, NT, NR>(acc, b, kuM, wl, kuM, otn, lane);
+            float v[NR];
+            acc_to_regs<NT, NR>(v, acc);
+            store_row<T, NR, false>(reinterpret_cast<T*>(a.din[s]) + (size_t)row * ks + c0, kb, v, h, valid);
+          }
+        } else if (a.din[s]) {
           const int otn = (ks + 31) / 32;
           __syncthreads();
           stage_block(wl, a.wtpk[0], kuM, koff / 32, otn, 0, kuM);
@@ -1165,8 +1201,17 @@ __global__ void reduce_partials_kernel(const float* __restrict__ p, int nw, int 
       hipLaunchKernelGGL((KERNEL<T, NT, MODE, false>), grid, dim3(BLOCK), 0, (hipStream_t)stream, *a); \
   } while (0)
 
+#define AGN_LAUNCH_WIDE(KERNEL, T, NT)                                                                      \
+  do {                                                                                                      \
+    if (a->act_fn != AGN_ACT_RELU)                                                                          \
+      hipLaunchKernelGGL((KERNEL<T, NT, M_GEN, true, true>), grid, dim3(BLOCK), 0, (hipStream_t)stream, *a);  \
+    else                                                                                                    \
+      hipLaunchKernelGGL((KERNEL<T, NT, M_GEN, false, true>), grid, dim3(BLOCK), 0, (hipStream_t)stream, *a); \
+  } while (0)
+
 #define AGN_FWD_MODES(T, NT)                                   \
   switch (mode) {                                              \
+    case M_WIDE: AGN_LAUNCH_WIDE(mlp_fwd_kernel, T, NT); break;    \
     case M_VEC: AGN_LAUNCH(mlp_fwd_kernel, T, NT, M_VEC); break;   \
     case M_NIN: AGN_LAUNCH(mlp_fwd_kernel, T, NT, M_NIN); break;   \
     case M_NOUT: AGN_LAUNCH(mlp_fwd_kernel, T, NT, M_NOUT); break; \
@@ -1174,6 +1219,7 @@ __global__ void reduce_partials_kernel(const float* __restrict__ p, int nw, int 
   }
 #define AGN_BWD_MODES(T, NT)                                   \
   switch (mode) {                                              \
+    case M_WIDE: AGN_LAUNCH_WIDE(mlp_bwd_kernel, T, NT); break;    \
     case M_VEC: AGN_LAUNCH(mlp_bwd_kernel, T, NT, M_VEC); break;   \
     case M_NOUT: AGN_LAUNCH(mlp_bwd_kernel, T, NT, M_NOUT); break; \
     default: AGN_LAUNCH(mlp_bwd_kernel, T, NT, M_GEN); break;      \
@@ -1313,8 +1359,14 @@ int agn_mlp_forward(const agn_mlp_fwd_args* a, void* stream) {
   const bool out_full =
       (a->out_ld % 8 == 0) && (a->nlin == 1 ? (a->out_dim % a->hidden == 0) : (a->out_dim == a->hidden));
   bool in_full = true;
+  bool wide = false;
   for (int s = 0; s < a->nseg; ++s) {
-    if (a->seg[s].k < 1 || a->seg[s].k > a->hidden) return AGN_E_SHAPE;
+    if (a->seg[s].k < 1 || a->seg[s].ld < a->seg[s].k) return AGN_E_SHAPE;
+    if (a->seg[s].k > a->hidden) {
+      // wider than hidden: a PLAIN / GATHER row walked in column blocks (never next to the projections)
+      if ((a->seg[s].kind != AGN_SEG_PLAIN && a->seg[s].kind != AGN_SEG_GATHER) || a->proj) return AGN_E_SHAPE;
+      wide = true;
+    }
     if (s + 1 < a->nseg && (a->seg[s].k % 32) != 0) return AGN_E_SHAPE;
     if (a->seg[s].k != a->hidden || a->seg[s].ld % 8 != 0) in_full = false;
   }
@@ -1331,6 +1383,7 @@ int agn_mlp_forward(const agn_mlp_fwd_args* a, void* stream) {
       mode = M_NIN;
     else if (in_full && a->nlin > 1 && a->out_dim <= 32 && !a->use_ln) mode = M_NOUT;
   }
+  if (wide) mode = M_WIDE;  // (never in_full, never M_NIN: always the masked-I/O mode)
   const bool vec = mode == M_VEC;
   if (g_opt_resident && vec) {  // a processor layer's node MLP: resident weights, aggregation walked in
     int rc = 0;
@@ -1359,10 +1412,19 @@ int agn_mlp_backward(const agn_mlp_bwd_args* a, void* stream) {
     return AGN_E_ARG;
   if (a->rows == 0) return 0;
   if (a->out_dim > a->hidden) return AGN_E_SHAPE;
+  long kin = 0;
+  bool wide = false;
   for (int s = 0; s < a->din_nseg; ++s) {
-    if (a->din_k[s] > a->hidden) return AGN_E_SHAPE;
+    if (a->din_k[s] < 1) return AGN_E_SHAPE;
+    if (a->din_k[s] > a->hidden) {
+      // wider than hidden: dX in column blocks into one [rows][k] buffer (no residual form)
+      if (a->din_resid[s]) return AGN_E_SHAPE;
+      wide = wide || a->din[s] != nullptr;
+    }
     if (s + 1 < a->din_nseg && (a->din_k[s] % 32) != 0) return AGN_E_SHAPE;
+    kin += a->din_k[s];
   }
+  if (wide && kin > a->in_dim) return AGN_E_SHAPE;  // the blocks index W0^T's packed rows
   if (a->act_fn < AGN_ACT_RELU || a->act_fn > AGN_ACT_TANH) return AGN_E_ARG;
   for (int l = 0; l + 1 < a->nlin; ++l) {
     // the ReLU backward reads the sign bits (AGN_RELU_MASK), the others the saved pre-activation
@@ -1374,7 +1436,7 @@ int agn_mlp_backward(const agn_mlp_bwd_args* a, void* stream) {
     if (a->out_dim == a->hidden) mode = M_VEC;
     else if (a->out_dim <= 32 && !a->use_ln) mode = M_NOUT;
   }
-  const bool vec = mode == M_VEC;
+  const bool vec = mode == M_VEC && !wide;
   agn_mlp_bwd_args* am = const_cast<agn_mlp_bwd_args*>(a);
   if (g_opt_resident && vec) {  // a processor layer's node MLP: resident weights
     int rc = 0, lr = 0;
@@ -1383,7 +1445,7 @@ int agn_mlp_backward(const agn_mlp_bwd_args* a, void* stream) {
       return rc;
     }
   }
-  if (g_opt_resident && mode == M_NOUT) {  // the decoder from H-wide rows: resident weights
+  if (g_opt_resident && mode == M_NOUT && !wide) {  // the decoder from H-wide rows: resident weights
     int rc = 0;
     if (agn::dec32_bwd_try(a, stream, &rc)) {
       am->ln_rows = (int)agn_mlp_bwd_nwaves(a->rows);
@@ -1398,6 +1460,7 @@ int agn_mlp_backward(const agn_mlp_bwd_args* a, void* stream) {
   }
   dim3 grid(agn_mlp_bwd_nwaves(a->rows));
   am->ln_rows = (int)grid.x;
+  if (wide) mode = M_WIDE;  // a wide dX that is wanted: the masked-I/O mode's WIDE instantiation
   AGN_DISPATCH(AGN_BWD_MODES);
   return launch_status();
 }

@@ -47,11 +47,16 @@ enum { AGN_ACT_RELU = 0, AGN_ACT_GELU = 1, AGN_ACT_SILU = 2, AGN_ACT_TANH = 3 };
 /* One input segment of a concatenated MLP input row (torch.cat in mgnLayer.py:44,151).
  * PLAIN : row r of ptr;  GATHER: row index[r] of ptr (x[row], x[col] of mgnLayer.py:40-41);
  * SUM/MEAN: sum (mean) of rows index[r] .. index[r+1]-1 of ptr (scatter_add / scatter_mean
- * of dst-grouped edges: index = CSC row pointer, rows grouped by receiver). */
+ * of dst-grouped edges: index = CSC row pointer, rows grouped by receiver).
+ * A PLAIN or GATHER segment may be wider than hidden (any k >= 1, e.g. poolMGN's node encoder on
+ * cat[x, global] with global_dim > 3 * hidden_dim): the kernel walks it in hidden-wide column
+ * blocks, accumulating in column order exactly as consecutive hidden-wide segments would. A SUM /
+ * MEAN segment, or any segment next to proj, stays <= hidden (AGN_E_SHAPE otherwise). Every
+ * segment but the last is a multiple of 32 wide. */
 typedef struct {
   int kind;
-  int k;          /* features in this segment (<= hidden) */
-  int ld;         /* row stride of ptr, elements */
+  int k;          /* features in this segment (>= 1; > hidden only for PLAIN / GATHER without proj) */
+  int ld;         /* row stride of ptr, elements (>= k) */
   int _pad;
   const void* ptr;
   const int32_t* index;
@@ -110,10 +115,10 @@ typedef struct {
   const int32_t* gidx;
   /* outputs */
   void* gpre[AGN_MAX_LIN];         /* dL/d(pre-activation of layer l), [rows][M_l] */
-  int din_nseg;                    /* segments of d(input of layer 0): widths din_k[s] */
-  int din_k[AGN_MAX_SEG];
-  void* din[AGN_MAX_SEG];          /* NULL = not needed */
-  int din_resid[AGN_MAX_SEG];      /* 1: din[s] = g(+g2) + W0^T dh0 (residual of the block) */
+  int din_nseg;                    /* segments of d(input of layer 0): widths din_k[s] >= 1, summing to in_dim */
+  int din_k[AGN_MAX_SEG];          /* > hidden: the segment's columns are computed in hidden-wide blocks */
+  void* din[AGN_MAX_SEG];          /* [rows][din_k[s]] (row stride din_k[s]); NULL = not needed */
+  int din_resid[AGN_MAX_SEG];      /* 1: din[s] = g(+g2) + W0^T dh0 (residual of the block; din_k[s] <= hidden) */
   float* ln_partial;               /* [agn_mlp_bwd_nwaves(rows)][2][out_dim]: sum g*xhat, sum g */
   int tiled;                       /* 1: act/hpre are read in the tiled layout */
   int gpre_tiled;                  /* bit l: gpre[l] written in the tiled layout (hidden-wide only) */
