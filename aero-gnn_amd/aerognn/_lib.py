@@ -116,6 +116,12 @@ class F64WgradArgs(C.Structure):
                 ("db", vp)]
 
 
+class AdamDesc(C.Structure):
+    _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", C.c_int64), ("dtype", i32), ("_pad", i32),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("step_size", C.c_double), ("bc2_sqrt", C.c_double)]
+
+
 _lib = None
 
 # Entry points that enqueue device work on a stream. When core.PROF is a list, every call of one
@@ -132,7 +138,7 @@ LAUNCHES = ("agn_pack", "agn_mlp_forward", "agn_mlp_backward", "agn_reduce_parti
             "agn_segment_max", "agn_segment_max_backward", "agn_edge_bwd_fused", "agn_encoder_bwd_fused", "agn_wgrad_reduce",
             "agn_edge_forward32", "agn_edge_agg_fixup",
             "agn_proj_forward", "agn_proj_backward", "agn_fourier_embed", "agn_fourier_embed_bwd", "agn_eval_sums",
-            "agn_aero_forces")
+            "agn_aero_forces", "agn_mse_loss", "agn_adam_step")
 
 
 class AeroGNNError(RuntimeError):
@@ -258,6 +264,11 @@ def lib():
             "agn_aero_forces_temp_bytes": (C.c_size_t, [i32, i32]),
             "agn_aero_forces": (i32, [i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, C.c_int64, vp, vp,
                                       C.c_double, vp, C.POINTER(C.c_double), vp, i32, vp, vp, vp]),
+            "agn_mse_chunk_rows": (i32, []),
+            "agn_mse_loss_temp_bytes": (C.c_size_t, [i32, i32]),
+            "agn_mse_loss": (i32, [i32, i32, i32, i32, vp, i32, vp, i32, C.c_double, vp, vp, vp, i32, vp, vp]),
+            "agn_adam_chunk_elems": (i32, []),
+            "agn_adam_step": (i32, [vp, i32, vp, i32, i32, vp]),
             "agn_f64_gemm": (i32, [C.POINTER(F64GemmArgs), vp]),
             "agn_f64_wgrad_scratch_bytes": (C.c_size_t, [C.POINTER(F64WgradArgs)]),
             "agn_f64_wgrad": (i32, [C.POINTER(F64WgradArgs), vp, vp]),

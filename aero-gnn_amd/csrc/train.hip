@@ -1,0 +1,251 @@
+// The training tail on the device: what the reference does with the prediction after `model(...)`
+// (utils.py:191-195 loss_fn(pred, y), loss.backward()'s first step, total_loss += loss.item();
+// train.py:207-212 with utils.py:193 torch.optim.Adam.step()).
+//
+// agn_mse_loss: ONE pass over pred and y gives the MSE value and its gradient. d = (double)pred -
+// (double)y; the squares and every sum are fp64. The reduction has two stages with a fixed tree
+// shape and no atomics (the manner of aero.hip): stage 1, one block per chunk of MSE_ROWS rows,
+// thread t takes the chunk's elements t, t + 256, ... in ascending order and the block adds its 256
+// threads in a halving tree; stage 2, one block, thread t adds the chunk partials t, t + 256, ... in
+// ascending order, the same tree adds the threads, and thread 0 alone writes S / n_global and adds it
+// to the epoch accumulator. The shape depends on (n, f) only: two calls give identical bytes.
+// dpred = (2 d) / n_global in fp64 with an IEEE division, rounded fp64 -> fp32 -> pred's dtype (RNE
+// at each step; once for fp64): the roundings of torch.Tensor.to() applied to the fp64 value.
+//
+// agn_adam_step: torch's single-tensor Adam (L2 weight decay, no amsgrad) for a whole parameter list
+// in one launch. A device-resident descriptor table holds one entry per tensor, a device-resident
+// chunk map cuts the list into (tensor, chunk) pairs of ADAM_CHUNK elements; the grid is capped and
+// walks the map with a grid stride. 16-B loads and stores where the tensor's four pointers allow it,
+// scalar otherwise. Every elementwise step is one correctly rounded operation in the tensor dtype, in
+// torch's order (the whole file is compiled with `#pragma clang fp contract(off)`: nothing is fused).
+#include "common.hpp"
+#include "host.hpp"
+#include "aerognn.h"
+
+using namespace agn;
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int MSE_ROWS = 2048;     // rows per stage-1 chunk
+constexpr int TR_THREADS = 256;
+constexpr int ADAM_CHUNK = 4096;   // elements per chunk-map entry (a multiple of 4: chunk starts keep the tensor's alignment)
+constexpr int ADAM_MAX_BLOCKS = 2048;
+
+// the sum of the block's 256 values in a fixed halving tree; thread 0 holds it on return
+AGN_DEV double block_tree_sum(double v, double* sh, int t) {
+  sh[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int h = TR_THREADS / 2; h >= 1; h >>= 1) {
+    if (t < h) sh[t] += sh[t + h];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// fp64 -> fp32 -> T with RNE at each step (fp64: one rounding, none)
+template <typename T> AGN_DEV T round_from_f64(double v) { return from_f<T>((float)v); }
+template <> AGN_DEV double round_from_f64<double>(double v) { return v; }
+template <> AGN_DEV float round_from_f64<float>(double v) { return (float)v; }
+
+// stage 1: part[b] = sum of d^2 over rows [b * MSE_ROWS, ...), dpred written on the way
+template <typename T, typename TY>
+__global__ void __launch_bounds__(TR_THREADS)
+mse_chunk_kernel(int n, int f, const T* __restrict__ pred, int pred_ld, const TY* __restrict__ y, int y_ld,
+                 double n_global, T* __restrict__ dpred, int dpred_ld, double* __restrict__ part) {
+  __shared__ double sh[TR_THREADS];
+  const int t = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * MSE_ROWS;
+  const int rows = (int)min((int64_t)MSE_ROWS, (int64_t)n - r0);  // >= 1: the grid is ceil(n / MSE_ROWS)
+  const int cnt = rows * f;                                       // <= MSE_ROWS * f, checked by the host
+  double s = 0.0;
+  for (int e = t; e < cnt; e += TR_THREADS) {
+    const int r = e / f, j = e - r * f;
+    const size_t row = (size_t)(r0 + r);
+    const double d = (double)pred[row * pred_ld + j] - (double)y[row * y_ld + j];
+    s += d * d;
+    if (dpred) dpred[row * dpred_ld + j] = round_from_f64<T>((2.0 * d) / n_global);
+  }
+  s = block_tree_sum(s, sh, t);
+  if (t == 0) part[blockIdx.x] = s;
+}
+
+// stage 2: loss = (sum of the partials, fixed order) / n_global; *acc += loss by thread 0 alone
+__global__ void __launch_bounds__(TR_THREADS)
+mse_finish_kernel(int nchunk, const double* __restrict__ part, double n_global, double* __restrict__ loss_out,
+                  double* __restrict__ acc) {
+  __shared__ double sh[TR_THREADS];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int c = t; c < nchunk; c += TR_THREADS) s += part[c];
+  s = block_tree_sum(s, sh, t);
+  if (t == 0) {
+    const double loss = s / n_global;
+    *loss_out = loss;
+    if (acc) *acc += loss;
+  }
+}
+
+template <typename T, typename TY>
+void launch_mse(int n, int f, const void* pred, int pred_ld, const void* y, int y_ld, double n_global, void* dpred,
+                int dpred_ld, double* part, hipStream_t st) {
+  const int nchunk = (int)(((int64_t)n + MSE_ROWS - 1) / MSE_ROWS);
+  hipLaunchKernelGGL((mse_chunk_kernel<T, TY>), dim3(nchunk), dim3(TR_THREADS), 0, st, n, f, (const T*)pred, pred_ld,
+                     (const TY*)y, y_ld, n_global, (T*)dpred, dpred_ld, part);
+}
+
+// ---------------------------------------------------------------------------- Adam
+template <typename T> AGN_DEV T sqrt_rn(T a);
+template <> AGN_DEV float sqrt_rn<float>(float a) { return __fsqrt_rn(a); }
+template <> AGN_DEV double sqrt_rn<double>(double a) { return sqrt(a); }
+template <typename T> AGN_DEV T quot_rn(T a, T b);
+template <> AGN_DEV float quot_rn<float>(float a, float b) { return __fdiv_rn(a, b); }
+template <> AGN_DEV double quot_rn<double>(double a, double b) { return a / b; }
+
+// the per-tensor scalars rounded to the tensor dtype (torch passes 1 - beta as one Python double)
+template <typename T>
+struct AdamK {
+  T omb1, beta1, beta2, omb2, eps, wd, step_size, bc2_sqrt;
+  bool decay, lerp_lo;  // lerp_lo: 1 - beta1 < 0.5, the branch of torch's lerp that starts from exp_avg
+};
+
+// one element, torch's _single_tensor_adam in its order:
+//   grad.add(param, alpha=wd); exp_avg.lerp_(grad, 1 - beta1); exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+//   denom = (exp_avg_sq.sqrt() / bc2_sqrt).add_(eps); param.addcdiv_(exp_avg, denom, value=-step_size)
+template <typename T>
+AGN_DEV void adam_elem(T& p, T g, T& m, T& v, const AdamK<T>& k) {
+  if (k.decay) g = g + k.wd * p;
+  m = k.lerp_lo ? m + k.omb1 * (g - m) : g - (g - m) * k.beta1;
+  v = v * k.beta2 + k.omb2 * (g * g);
+  const T denom = quot_rn<T>(sqrt_rn<T>(v), k.bc2_sqrt) + k.eps;
+  p = p - k.step_size * quot_rn<T>(m, denom);
+}
+
+template <typename T> struct Vec16;
+template <> struct Vec16<float> { typedef f32x4 type; static constexpr int W = 4; };
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+template <> struct Vec16<double> { typedef f64x2 type; static constexpr int W = 2; };
+
+template <typename T>
+__global__ void __launch_bounds__(TR_THREADS)
+adam_kernel(const agn_adam_desc* __restrict__ descs, int ntensor, const int32_t* __restrict__ cmap, int nchunk,
+            int dtype) {
+  typedef typename Vec16<T>::type V;
+  constexpr int W = Vec16<T>::W;
+  const int t = threadIdx.x;
+  for (int c = blockIdx.x; c < nchunk; c += gridDim.x) {  // block-uniform walk of the chunk map
+    const int ti = cmap[2 * c], ci = cmap[2 * c + 1];
+    if (ti < 0 || ti >= ntensor || ci < 0) continue;     // a malformed map entry touches nothing
+    const agn_adam_desc d = descs[ti];
+    if (d.dtype != dtype || !d.p || !d.g || !d.m || !d.v) continue;
+    const int64_t e0 = (int64_t)ci * ADAM_CHUNK;
+    if (e0 >= d.n) continue;                              // n == 0: a parameter without a gradient
+    const int len = (int)min((int64_t)ADAM_CHUNK, d.n - e0);
+    AdamK<T> k;
+    k.omb1 = (T)(1.0 - d.beta1);
+    k.beta1 = (T)1 - k.omb1;
+    k.lerp_lo = fabs((double)k.omb1) < 0.5;  // torch's lerp tests the weight as rounded to the tensor dtype
+    k.beta2 = (T)d.beta2;
+    k.omb2 = (T)(1.0 - d.beta2);
+    k.eps = (T)d.eps;
+    k.wd = (T)d.weight_decay;
+    k.decay = d.weight_decay != 0.0;
+    k.step_size = (T)d.step_size;
+    k.bc2_sqrt = (T)d.bc2_sqrt;
+    T* p = (T*)d.p + e0;
+    const T* g = (const T*)d.g + e0;
+    T* m = (T*)d.m + e0;
+    T* v = (T*)d.v + e0;
+    // e0 * sizeof(T) is a multiple of 16, so the chunk is aligned exactly when the tensor is
+    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                       reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    const int nv = vec ? len / W : 0;
+    for (int i = t; i < nv; i += TR_THREADS) {
+      V pv = reinterpret_cast<V*>(p)[i], mv = reinterpret_cast<V*>(m)[i], vv = reinterpret_cast<V*>(v)[i];
+      const V gv = reinterpret_cast<const V*>(g)[i];
+#pragma unroll
+      for (int q = 0; q < W; ++q) {
+        T pe = pv[q], me = mv[q], ve = vv[q];
+        adam_elem<T>(pe, gv[q], me, ve, k);
+        pv[q] = pe; mv[q] = me; vv[q] = ve;
+      }
+      reinterpret_cast<V*>(p)[i] = pv;
+      reinterpret_cast<V*>(m)[i] = mv;
+      reinterpret_cast<V*>(v)[i] = vv;
+    }
+    for (int i = nv * W + t; i < len; i += TR_THREADS) adam_elem<T>(p[i], g[i], m[i], v[i], k);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int agn_mse_chunk_rows(void) { return MSE_ROWS; }
+
+size_t agn_mse_loss_temp_bytes(int n, int f) {
+  if (n < 0 || f < 1) return 0;
+  const size_t nchunk = (size_t)(((int64_t)n + MSE_ROWS - 1) / MSE_ROWS);
+  return (sizeof(double) * (nchunk > 0 ? nchunk : 1) + 15) & ~(size_t)15;
+}
+
+int agn_mse_loss(int dtype, int y_dtype, int n, int f, const void* pred, int pred_ld, const void* y, int y_ld,
+                 double n_global, double* loss_out, double* acc, void* dpred, int dpred_ld, void* scratch,
+                 void* stream) {
+  if (n < 0) return AGN_E_ARG;
+  if (dtype != AGN_F32 && dtype != AGN_BF16 && dtype != AGN_F16 && dtype != AGN_F64) return AGN_E_DTYPE;
+  if (y_dtype != dtype && y_dtype != AGN_F32) return AGN_E_DTYPE;
+  // f <= 2^31 / MSE_ROWS keeps a chunk's element count in an int
+  if (f < 1 || f > (1 << 19) || pred_ld < f || y_ld < f || (dpred && dpred_ld < f)) return AGN_E_SHAPE;
+  if (!(n_global > 0.0)) return AGN_E_SHAPE;
+  if (!loss_out) return AGN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {  // loss 0, acc unchanged: a plain memset of the 8 bytes, no kernel
+    const hipError_t e = hipMemsetAsync(loss_out, 0, sizeof(double), st);
+    return e == hipSuccess ? 0 : (int)e;
+  }
+  if (!pred || !y || !scratch) return AGN_E_ARG;
+  double* part = reinterpret_cast<double*>(scratch);
+  const bool ysame = y_dtype == dtype;
+  switch (dtype) {
+    case AGN_F32: launch_mse<float, float>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st); break;
+    case AGN_F64:
+      if (ysame) launch_mse<double, double>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
+      else launch_mse<double, float>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
+      break;
+    case AGN_BF16:
+      if (ysame) launch_mse<bf16, bf16>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
+      else launch_mse<bf16, float>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
+      break;
+    default:
+      if (ysame) launch_mse<f16, f16>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
+      else launch_mse<f16, float>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
+      break;
+  }
+  const int nchunk = (int)(((int64_t)n + MSE_ROWS - 1) / MSE_ROWS);
+  hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(TR_THREADS), 0, st, nchunk, part, n_global, loss_out, acc);
+  return launch_status();
+}
+
+int agn_adam_chunk_elems(void) { return ADAM_CHUNK; }
+
+int agn_adam_step(const agn_adam_desc* descs_device, int ntensor, const int32_t* chunk_map_device, int nchunk,
+                  int dtype, void* stream) {
+  if (ntensor < 0 || nchunk < 0) return AGN_E_ARG;
+  if (dtype != AGN_F32 && dtype != AGN_F64) return AGN_E_DTYPE;
+  if (ntensor == 0 || nchunk == 0) return 0;
+  if (!descs_device || !chunk_map_device) return AGN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = nchunk < ADAM_MAX_BLOCKS ? nchunk : ADAM_MAX_BLOCKS;
+  if (dtype == AGN_F32)
+    hipLaunchKernelGGL(adam_kernel<float>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor, chunk_map_device,
+                       nchunk, dtype);
+  else
+    hipLaunchKernelGGL(adam_kernel<double>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor,
+                       chunk_map_device, nchunk, dtype);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -601,6 +601,63 @@ int agn_aero_forces(int dtype, int n, int dim, const void* pressure, const void*
                     double length_scale, double* area_out, const double* center, const int32_t* gptr, int ngraph,
                     double* out, void* scratch, void* stream);
 
+/* ---- the training tail on the device: fused MSE loss + gradient, multi-tensor Adam.
+ * Replaces (reference file:line): utils.py:191-192,195 (loss_fn(pred, batch.y) with nn.MSELoss, the
+ * first step of loss.backward(), total_loss += loss.item()) and aerognn.dist.mse_sum_loss;
+ * train.py:207-212 (torch.optim.Adam with L2 weight decay) together with utils.py:193 (optimizer.step()).
+ *
+ * agn_mse_loss: pred [n][f] (row stride pred_ld) of dtype AGN_F32 / AGN_BF16 / AGN_F16 / AGN_F64, y [n][f]
+ *   (row stride y_ld) of y_dtype = dtype or AGN_F32; n_global: the element count the mean is taken over
+ *   (n * f, or the all-reduced count under data parallelism). With d = (double)pred - (double)y:
+ *     *loss_out = S / n_global, S = sum d^2; squares and sums in fp64, two stages with a fixed tree
+ *       shape and no atomics (per-chunk partials of agn_mse_chunk_rows rows each, then one block adds
+ *       the partials in a fixed order): two calls give identical bytes
+ *     *acc += *loss_out (acc may be NULL): the epoch accumulator, added by one thread of the second stage
+ *     dpred [n][f] (row stride dpred_ld, pred's dtype; may be NULL: evaluation) = (2 d) / n_global,
+ *       evaluated in fp64 with an IEEE division, then rounded fp64 -> fp32 -> pred's dtype with RNE at
+ *       each step (AGN_F64: no rounding after the division), as torch.Tensor.to() rounds a double
+ *   scratch: agn_mse_loss_temp_bytes(n, f) bytes, 16-B aligned. Errors: AGN_E_ARG (null pointer, n < 0),
+ *   AGN_E_DTYPE, AGN_E_SHAPE (f < 1, a row stride narrower than the row, n_global <= 0). n == 0 writes a
+ *   loss of 0, leaves acc unchanged and launches no kernel.
+ *
+ * agn_adam_step: one launch updates every tensor of dtype `dtype` (AGN_F32 or AGN_F64) in a
+ *   device-resident table of ntensor descriptors; entries of the other dtype, with a null pointer or
+ *   with n == 0 (a parameter whose .grad is None) are skipped. step_size = lr / (1 - beta1^t) and
+ *   bc2_sqrt = sqrt(1 - beta2^t) are formed by the host in double from the tensor's own step count t,
+ *   as torch's single-tensor Adam forms them; the kernel rounds the scalars to the tensor dtype
+ *   (1 - beta1 and 1 - beta2 are subtracted in double first). Per element, every operation rounded
+ *   once in the tensor dtype, nothing fused:
+ *     g' = g + weight_decay * p                  (only when weight_decay != 0: L2, not decoupled)
+ *     m  = m + (1 - beta1) * (g' - m)            (torch's lerp_; g' - (g' - m) * beta1 when 1 - beta1 >= 0.5)
+ *     v  = v * beta2 + (1 - beta2) * (g' * g')
+ *     p  = p - step_size * (m / (sqrt(v) / bc2_sqrt + eps))
+ *   chunk_map_device: int32 [nchunk][2] = (tensor index, chunk index); chunk c of a tensor covers its
+ *   elements [c * E, min(n, (c + 1) * E)), E = agn_adam_chunk_elems. Every (tensor, chunk) pair may
+ *   appear at most once. An entry outside the table or past the tensor's end touches nothing. The
+ *   grid is capped at 2048 blocks that walk the map with a grid stride. 16-B loads and stores where a
+ *   tensor's four pointers are 16-B aligned (scalar tail), scalar otherwise.
+ *   Errors: AGN_E_ARG (a null table or map, a negative count), AGN_E_DTYPE. */
+typedef struct {
+  void* p;            /* parameter, n elements, updated in place */
+  const void* g;      /* gradient */
+  void* m;            /* exp_avg, updated in place */
+  void* v;            /* exp_avg_sq, updated in place */
+  int64_t n;
+  int dtype;          /* AGN_F32 / AGN_F64, of all four */
+  int _pad;
+  double beta1, beta2, eps, weight_decay;
+  double step_size;   /* lr / (1 - beta1^t) */
+  double bc2_sqrt;    /* sqrt(1 - beta2^t) */
+} agn_adam_desc;
+int agn_mse_chunk_rows(void);
+size_t agn_mse_loss_temp_bytes(int n, int f);
+int agn_mse_loss(int dtype, int y_dtype, int n, int f, const void* pred, int pred_ld, const void* y, int y_ld,
+                 double n_global, double* loss_out, double* acc, void* dpred, int dpred_ld, void* scratch,
+                 void* stream);
+int agn_adam_chunk_elems(void);
+int agn_adam_step(const agn_adam_desc* descs_device, int ntensor, const int32_t* chunk_map_device, int nchunk,
+                  int dtype, void* stream);
+
 /* ---- float64 mode (train.py:20-40 precision "double" / "float64"): the MLP / GMP path in fp64
  * on plain LDS-tiled FMA kernels (csrc/f64.hip); graph ops take dtype AGN_F64. */
 typedef struct {
