@@ -138,7 +138,7 @@ LAUNCHES = ("agn_pack", "agn_mlp_forward", "agn_mlp_backward", "agn_reduce_parti
             "agn_segment_max", "agn_segment_max_backward", "agn_edge_bwd_fused", "agn_encoder_bwd_fused", "agn_wgrad_reduce",
             "agn_edge_forward32", "agn_edge_agg_fixup",
             "agn_proj_forward", "agn_proj_backward", "agn_fourier_embed", "agn_fourier_embed_bwd", "agn_eval_sums",
-            "agn_aero_forces", "agn_mse_loss", "agn_adam_step")
+            "agn_aero_forces", "agn_surface_forces", "agn_face_edges", "agn_mse_loss", "agn_adam_step")
 
 
 class AeroGNNError(RuntimeError):
@@ -264,6 +264,11 @@ def lib():
             "agn_aero_forces_temp_bytes": (C.c_size_t, [i32, i32]),
             "agn_aero_forces": (i32, [i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, C.c_int64, vp, vp,
                                       C.c_double, vp, C.POINTER(C.c_double), vp, i32, vp, vp, vp]),
+            "agn_surface_forces_temp_bytes": (C.c_size_t, [i32, i32, i32]),
+            "agn_surface_forces": (i32, [i32, i32, vp, i32, i32, vp, vp, C.c_int64, i32, i32, i32, C.POINTER(vp),
+                                         C.POINTER(i32), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+            "agn_face_edges_temp_bytes": (C.c_size_t, [C.c_int64]),
+            "agn_face_edges": (i32, [i32, i32, vp, vp, C.c_int64, i32, vp, C.c_int64, vp, vp, vp]),
             "agn_mse_chunk_rows": (i32, []),
             "agn_mse_loss_temp_bytes": (C.c_size_t, [i32, i32]),
             "agn_mse_loss": (i32, [i32, i32, i32, i32, vp, i32, vp, i32, C.c_double, vp, vp, vp, i32, vp, vp]),

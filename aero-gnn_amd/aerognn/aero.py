@@ -11,6 +11,10 @@ agn_aero_forces); only a few dozen doubles per case travel to the host.
   node_areas(pos, edge_index, length_scale=1e-2)              -> float64 [n]
   integrate_forces(pressure, shear, normals, ...)             -> ForceSums of [G, ...] tensors
   calculate_aero_coefficients_2d / _3d                        -> the reference's names and keys
+  calculate_aero_coefficients_3d_mesh(pos, faces, true, pred) -> CA_true .. CY_pred from points and faces:
+                                                                 cell areas, normals, point-to-cell means and
+                                                                 force sums in ONE pass (aerognn.surface,
+                                                                 torch.ops.aerognn.surface_forces)
   DeviceEvaluator(model, norm_stats, params)                  -> AeroInference without host copies
 
 Sums are fp64, deterministic (fixed-order two-stage reductions, no atomics) and batch independent:
@@ -236,6 +240,28 @@ def calculate_aero_coefficients_3d(areas, normals, pressure, shear_stress, refer
     return {"CA": float(c[0, 0]), "CN": float(c[0, 1]), "CY": float(c[0, 2])}
 
 
+def calculate_aero_coefficients_3d_mesh(pos, faces, true_fields, pred_fields, reference_area: float = 1.0,
+                                        dynamic_pressure: float = 1.0, stats=None) -> dict:
+    """inference.py:310-320 followed by utils.py:385-448 from the mesh itself: pos [N, 3], a face list
+    (aerognn.surface.faces_csr's formats; consistently wound) and the true and predicted point fields
+    [N, 4] (pressure, tau_x, tau_y, tau_z). Cell areas, cell normals, the point-to-cell means of both
+    sets and the force sums are ONE surface_forces pass. With stats (norm_stats) both sets are
+    de-normalised first. Returns the reference's six keys CA_true .. CY_pred (utils.py:441-448)."""
+    c = coefficients_3d_mesh(pos, faces, [true_fields, pred_fields], reference_area, dynamic_pressure, stats)
+    return {f"{k}_{nm}": float(c[k][0, s]) for s, nm in enumerate(("true", "pred")) for k in ("CA", "CN", "CY")}
+
+
+def coefficients_3d_mesh(pos, faces, fields, reference_area=1.0, dynamic_pressure=1.0, stats=None, cell_batch=None,
+                         ngraph=None) -> dict:
+    """numpy [G, nset] arrays CA, CN, CY and their scales S_CA, S_CN, S_CY (the sums of absolute
+    contributions, normalised like the coefficient) for up to four field sets in one pass."""
+    from .surface import integrate_surface
+    ss = integrate_surface(pos, faces, fields, stats=stats, cell_batch=cell_batch, ngraph=ngraph)
+    h = torch.stack([ss.force, ss.abs_force]).cpu().numpy() / float(reference_area) / float(dynamic_pressure)
+    return {"CA": h[0, :, :, 0], "CN": h[0, :, :, 1], "CY": h[0, :, :, 2],
+            "S_CA": h[1, :, :, 0], "S_CN": h[1, :, :, 1], "S_CY": h[1, :, :, 2]}
+
+
 # ----------------------------------------------------------------------------- AeroInference
 class DeviceEvaluator:
     """AeroInference (inference.py:29-473) without host copies, plots or VTU export: evaluate_case
@@ -295,6 +321,11 @@ class DeviceEvaluator:
             coeff_str = (f" | CA:{pc['CA']:7.4f} ({tc['CA']:7.4f}) "
                          f"| CN:{pc['CN']:7.4f} ({tc['CN']:7.4f}) "
                          f"| Cm:{pc['Cm']:7.4f} ({tc['Cm']:7.4f})")
+        elif self._ds().get("name", "dataset") == "ahmed_body" and getattr(data, "faces", None) is not None:
+            c = self._ahmed_coefficients(data, y, pred)
+            coeff_str = (f" | CA:{c['CA_pred']:7.4f} ({c['CA_true']:7.4f}) "
+                         f"| CN:{c['CN_pred']:7.4f} ({c['CN_true']:7.4f}) "
+                         f"| CY:{c['CY_pred']:7.4f} ({c['CY_true']:7.4f})")
         info = {"case_id": len(self.cases),
                 "rrmse_percent": rep.rrmse_percent(0, "physical"),
                 "errors_physical": rep.feature_errors(0, "physical", names),
@@ -307,6 +338,26 @@ class DeviceEvaluator:
         self.cases.append(info)
         self._reports.append(rep)
         return info
+
+    def _ahmed_coefficients(self, data, y, pred) -> dict:
+        """inference.py:298-327 from data.pos and data.faces instead of the case's .vtp: the six
+        coefficients with q = 0.5 * 1.225 * Velocity^2 and reference_area = Height * Width * 1e-6 / 2.
+        The reference's "true" fields are the file's own cell data: data.cell_y ([C, 4], physical) is
+        used when the case carries it, otherwise the point-to-cell mean of the de-normalised y."""
+        from .surface import integrate_surface
+        num = lambda v: float(v.reshape(-1)[0]) if torch.is_tensor(v) else float(v)  # noqa: E731
+        velocity, height, width = num(data.Velocity), num(data.Height), num(data.Width)
+        kw = dict(reference_area=height * width * 1e-6 / 2, dynamic_pressure=0.5 * 1.225 * velocity * velocity)
+        cell_y = getattr(data, "cell_y", None)
+        if cell_y is None:
+            return calculate_aero_coefficients_3d_mesh(data.pos, data.faces, y[:, :4], pred[:, :4],
+                                                       stats=self.device_norm_stats, **kw)
+        ss = integrate_surface(data.pos, data.faces, pred[:, :4], stats=self.device_norm_stats, return_cells=True)
+        cp = ss.force[0, 0].cpu().numpy() / kw["reference_area"] / kw["dynamic_pressure"]
+        cell_y = cell_y.to(self.device)
+        ct = calculate_aero_coefficients_3d(ss.areas, ss.normals.to(cell_y.dtype), cell_y[:, 0], cell_y[:, 1:4], **kw)
+        return {"CA_true": ct["CA"], "CN_true": ct["CN"], "CY_true": ct["CY"],
+                "CA_pred": float(cp[0]), "CN_pred": float(cp[1]), "CY_pred": float(cp[2])}
 
     def test_set_mean(self) -> dict:
         names = self._ds().get("output_features", None)

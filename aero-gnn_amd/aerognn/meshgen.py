@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["ellipsoid", "collate", "num_edges"]
+__all__ = ["ellipsoid", "lattice_faces", "collate", "num_edges"]
 
 
 def num_edges(nu: int, nv: int) -> int:
@@ -106,6 +106,20 @@ def ellipsoid(nu: int, nv: int, a: float = 4.0, b: float = 1.0, c: float = 1.0,
     y = rng.standard_normal((N, 4)).astype(dtype)
     return dict(pos=pos.astype(dtype), normals=nrm.astype(dtype), x=x, edge_attr=edge_attr,
                 y=y, edge_index=ei)
+
+
+def lattice_faces(nu: int, nv: int) -> np.ndarray:
+    """The triangles of `ellipsoid`'s lattice, int64 [2 * nu * (nv - 1), 3]: per node (ring j < nv - 1,
+    position i) the pair (nid, right_below, right), (nid, nid_below, right_below), pairs in node order.
+    Consistently wound with outward normals; their sides are exactly ellipsoid(nu, nv)["edge_index"]."""
+    i = np.arange(nu)
+    j = np.arange(nv)
+    nid = (j[:, None] * nu + i[None, :])
+    right = (j[:, None] * nu + (i[None, :] + 1) % nu)
+    a, r = nid[:-1].ravel(), right[:-1].ravel()
+    b, rb = nid[1:].ravel(), right[1:].ravel()
+    pair = np.stack([np.stack([a, rb, r], 1), np.stack([a, b, rb], 1)], 1)   # [nodes, 2, 3]
+    return pair.reshape(-1, 3).astype(np.int64)
 
 
 def collate(meshes: list[dict]) -> dict:

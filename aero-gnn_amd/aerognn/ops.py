@@ -32,6 +32,11 @@ torch.compile / FakeTensorMode, and autograd formulas that are themselves torch.
               length_scale=1e-2) -> (float64 [G, 4, 3] = sum F, sum M, sum |F|, sum |M|; areas float64 [n])
       surface integration of utils.py:385-448 / :451-559 with either the given element areas or
       the node areas of utils.py:510-520 from the mesh: agn_aero_forces. No autograd (evaluation).
+  surface_forces(pos? [N,3], offsets? int64 [C+1], conn int64 [nconn] or [C,k], fields [N,4] x 0..4, mean?, std?,
+                 cgptr int32 [G+1], want_cells=False)
+      -> (float64 [G, nset, 2, 3] = sum F, sum |F|; areas float64 [C]; normals float64 [C, 3]; cells [nset, C, 4])
+      cell areas, cell normals, point-to-cell means and the force sums of a 3-D surface given as points and
+      a face list, one pass (inference.py:310-320 + utils.py:385-448): agn_surface_forces. No autograd.
 
 The fused MLP / MeshGraphNet-layer kernels are not registered as operators: their calls carry
 packed-weight caches and a per-level CSC plan (Python objects), so they stay
@@ -405,6 +410,91 @@ def _(pressure, shear, normals, pos, areas, edge_index, gptr, center, length_sca
     n = shear.shape[0] if edge_index is not None else 0
     return (shear.new_empty(gptr.shape[0] - 1, 4, 3, dtype=torch.float64),
             shear.new_empty(n, dtype=torch.float64))
+
+
+@torch.library.custom_op("aerognn::surface_forces", mutates_args=())
+def surface_forces(pos: Optional[Tensor], offsets: Optional[Tensor], conn: Tensor, fields: list[Tensor],
+                   mean: Optional[Tensor], std: Optional[Tensor], cgptr: Tensor,
+                   want_cells: bool = False) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(sums [G, nset, 2, 3] float64 = sum F, sum |F|; areas float64 [C]; normals float64 [C, 3]; cells
+    [nset, C, 4] of the field dtype). Without want_cells the three cell outputs are empty ([0], [0, 3],
+    [0, C, 4]); without pos the geometry is skipped (point-to-cell means alone) and areas / normals are
+    empty. pos and the fields may be fp32 or fp64 independently (the geometry is fp64 either way: an fp32
+    pos gives what its exact fp64 copy gives); bf16 / fp16 inputs are widened to fp32 first."""
+    import ctypes as C
+    from ._lib import check, lib, ptr
+    from .core import dt_code, stream
+    require_device(pos, offsets, conn, mean, std, cgptr, *fields)
+    nset = len(fields)
+    if nset > 4:
+        raise ValueError("surface_forces: at most four field sets")
+    if pos is None and nset == 0:
+        raise ValueError("surface_forces: nothing to do without pos and without fields")
+    if pos is not None and (pos.dim() != 2 or pos.shape[1] != 3):
+        raise ValueError("surface_forces: pos must be [N, 3]")
+    n = pos.shape[0] if pos is not None else fields[0].shape[0]
+    if any(f.dim() != 2 or f.shape != (n, 4) for f in fields):
+        raise ValueError("surface_forces: every field set must be [N, 4] (pressure, tau_x, tau_y, tau_z)")
+    if (mean is None) != (std is None):
+        raise ValueError("surface_forces: give mean and std together")
+    if offsets is None:
+        if conn.dim() != 2:
+            raise ValueError("surface_forces: without offsets conn must be [C, k]")
+        ncell, k = conn.shape
+    else:
+        if conn.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError("surface_forces: the CSR form takes offsets [C + 1] and a flat conn")
+        ncell, k = offsets.numel() - 1, 0
+        offsets = offsets.to(torch.int64).contiguous()
+    conn = conn.to(torch.int64).contiguous()
+    nconn = conn.numel()
+    if nconn:
+        lo, hi = torch.stack(list(torch.aminmax(conn))).tolist()  # one copy to the host
+        if lo < 0 or hi >= n:
+            raise IndexError(f"surface_forces: face ids out of range [0, {n})")
+    dev = conn.device
+    pos = None if pos is None else _embed_rows(_wide(pos), "surface_forces")
+    fields = [_embed_rows(_wide(f), "surface_forces") for f in fields]
+    fdt = fields[0].dtype if nset else (pos.dtype if pos is not None else torch.float32)
+    fields = [f if f.dtype == fdt else f.to(fdt) for f in fields]
+    if mean is not None:
+        mean, std = _wide(mean, fdt).reshape(-1).contiguous(), _wide(std, fdt).reshape(-1).contiguous()
+        if mean.numel() != 4 or std.numel() != 4:
+            raise ValueError("surface_forces: mean and std must have four entries")
+    cgptr = _check_gptr(cgptr, "surface_forces")
+    G = cgptr.numel() - 1
+    launch = ncell > 0 and G > 0
+    out = (torch.empty if launch and nset else torch.zeros)(G, nset, 2, 3, dtype=torch.float64, device=dev)
+    geo = want_cells and pos is not None
+    areas = torch.empty(ncell if geo else 0, dtype=torch.float64, device=dev)
+    normals = torch.empty(ncell if geo else 0, 3, dtype=torch.float64, device=dev)
+    cells = torch.empty(nset if want_cells else 0, ncell, 4, dtype=fdt, device=dev)
+    if not launch:
+        return out, areas, normals, cells
+    scratch = torch.empty(int(lib().agn_surface_forces_temp_bytes(ncell, G, nset)), dtype=torch.uint8, device=dev)
+    fptr = (C.c_void_p * max(nset, 1))(*[f.data_ptr() for f in fields])
+    fld = (C.c_int * max(nset, 1))(*[max(f.stride(0), 4) for f in fields])
+    check(lib().agn_surface_forces(dt_code(pos.dtype) if pos is not None else dt_code(fdt), n, ptr(pos),
+                                   0 if pos is None else max(pos.stride(0), 3), ncell, ptr(offsets), ptr(conn), nconn, k,
+                                   dt_code(fdt), nset, fptr, fld, ptr(mean), ptr(std), ptr(cgptr), G,
+                                   ptr(out) if nset else None, ptr(areas) if geo else None,
+                                   ptr(normals) if geo else None, ptr(cells) if want_cells and nset else None,
+                                   ptr(scratch), stream()), "surface_forces")
+    return out, areas, normals, cells
+
+
+@surface_forces.register_fake
+def _(pos, offsets, conn, fields, mean, std, cgptr, want_cells=False):
+    ncell = conn.shape[0] if offsets is None else offsets.shape[0] - 1
+    nset = len(fields)
+    fdt = fields[0].dtype if nset else (pos.dtype if pos is not None else torch.float32)
+    if fdt in (torch.bfloat16, torch.float16):
+        fdt = torch.float32
+    geo = want_cells and pos is not None
+    return (conn.new_empty(cgptr.shape[0] - 1, nset, 2, 3, dtype=torch.float64),
+            conn.new_empty(ncell if geo else 0, dtype=torch.float64),
+            conn.new_empty(ncell if geo else 0, 3, dtype=torch.float64),
+            conn.new_empty(nset if want_cells else 0, ncell, 4, dtype=fdt))
 
 
 # ------------------------------------------------------------------------------- PyG-style pools

@@ -6,8 +6,8 @@
 // prediction to the host and runs ~20 torch.mean passes per case; here each quantity is one pass
 // over the device arrays plus one finishing pass.
 //
-// Reductions (both entries): fp64 accumulators, two stages, no atomics and nothing passed between
-// workgroups. Stage 1: one block per chunk of AERO_ROWS rows; chunks are laid out from each graph's
+// Reductions (both entries; the code is in aero_reduce.hpp, shared with surface.hip): fp64
+// accumulators, two stages, no atomics and nothing passed between workgroups. Stage 1: one block per chunk of AERO_ROWS rows; chunks are laid out from each graph's
 // first row (not from row 0 of the batch), so graph g of a batch is cut exactly as it is when it
 // is evaluated alone. Thread t owns one column j = t % f and takes the chunk's elements t, t + S,
 // t + 2 S, ... (S = the largest multiple of f <= 256) in ascending order; the block then adds the
@@ -30,69 +30,17 @@
 #include "host.hpp"
 #include "aerognn.h"
 
-using namespace agn;
-
 #pragma clang fp contract(off)
+
+#include "aero_reduce.hpp"  // chunk layout, the block tree and the finishing pass (shared with surface.hip)
+
+using namespace agn;
+using namespace agn::red;
 
 namespace {
 
-constexpr int AERO_ROWS = 2048;   // rows (or elements) per chunk
-constexpr int AERO_THREADS = 256;
 constexpr int AERO_NACC = 12;     // fp64 accumulators per thread, both entries
 constexpr int AERO_MAX_F = 16;
-
-// the chunk-count prefix `coff` [ngraph + 1] -> (graph, first row, end row) of block b; false past the total.
-// Row ranges are clamped to [0, n], so a malformed gptr cannot send a read out of the arrays.
-AGN_DEV bool find_chunk(int b, int n, int ngraph, const int32_t* __restrict__ gptr, const int32_t* __restrict__ coff,
-                        int* g_out, int* r0_out, int* r1_out) {
-  if (b >= coff[ngraph]) return false;
-  int lo = 0, hi = ngraph;  // last g with coff[g] <= b (empty graphs share an offset: the last one wins)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (coff[mid] <= b) lo = mid;
-    else hi = mid;
-  }
-  const int g = lo;
-  const int a = max(gptr[g], 0), e = min(gptr[g + 1], n);
-  const int64_t r0 = (int64_t)a + (int64_t)(b - coff[g]) * AERO_ROWS;
-  if (r0 >= e) return false;
-  *g_out = g;
-  *r0_out = (int)r0;
-  *r1_out = (int)min((int64_t)e, r0 + AERO_ROWS);
-  return true;
-}
-
-// cnt[g] = chunks of graph g
-__global__ void chunk_count_kernel(int n, int ngraph, const int32_t* __restrict__ gptr, int32_t* __restrict__ cnt) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= ngraph) return;
-  const int a = max(gptr[g], 0), e = min(gptr[g + 1], n);
-  cnt[g] = e > a ? (e - a + AERO_ROWS - 1) / AERO_ROWS : 0;
-}
-
-// Adds, per column j, the accumulators of the Q threads t = q * f + j (q < Q) in a halving tree over
-// q; on return the threads with q == 0 hold the sums. sh: [AERO_NACC][AERO_THREADS] doubles.
-AGN_DEV void column_tree_reduce(double (&a)[AERO_NACC], double (*sh)[AERO_THREADS], int t, int f, int Q) {
-  const int q = t / f;
-  const bool live = q < Q;
-#pragma unroll
-  for (int k = 0; k < AERO_NACC; ++k)
-    if (live) sh[k][t] = a[k];
-  __syncthreads();
-  int P = 1;
-  while (P < Q) P <<= 1;
-  for (int h = P >> 1; h >= 1; h >>= 1) {
-    if (live && q < h && q + h < Q) {
-#pragma unroll
-      for (int k = 0; k < AERO_NACC; ++k) sh[k][t] += sh[k][t + h * f];
-    }
-    __syncthreads();
-  }
-  if (live && q == 0) {
-#pragma unroll
-    for (int k = 0; k < AERO_NACC; ++k) a[k] = sh[k][t];
-  }
-}
 
 template <typename T> AGN_DEV T div_rn(T a, T b);
 template <> AGN_DEV float div_rn<float>(float a, float b) { return __fdiv_rn(a, b); }
@@ -138,7 +86,7 @@ eval_chunk_kernel(int n, int f, int ngraph, const T* __restrict__ pred, int pred
       error_terms<T>(a + 6, pp, tp);                           // physical scale
     }
   }
-  column_tree_reduce(a, sh, t, f, Q);
+  column_tree_reduce<AERO_NACC>(a, sh, t, f, Q);
   if (t < f) {
     double* o = part + (size_t)blockIdx.x * (AERO_NACC * f);
 #pragma unroll
@@ -147,26 +95,6 @@ eval_chunk_kernel(int n, int f, int ngraph, const T* __restrict__ pred, int pred
       o[((size_t)f + t) * 6 + k] = a[6 + k];
     }
   }
-}
-
-// stage 2 (both entries): out[g][o] = sum over the graph's chunks, ascending, of part[chunk][o]; o < width
-__global__ void finish_kernel(int ngraph, int width, int cap, const int32_t* __restrict__ coff,
-                              const double* __restrict__ part, double* __restrict__ out) {
-  const int g = blockIdx.x, o = threadIdx.x;
-  if (o >= width) return;
-  const int c0 = max(coff[g], 0), c1 = min(coff[g + 1], cap);  // cap = chunks the partials hold
-  double s = 0.0;
-  int c = c0;
-  // eight loads in flight, then their adds in ascending chunk order (the order of the plain loop)
-  for (; c + 8 <= c1; c += 8) {
-    double v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = part[(size_t)(c + i) * width + o];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += v[i];
-  }
-  for (; c < c1; ++c) s += part[(size_t)c * width + o];
-  out[(size_t)g * width + o] = s;
 }
 
 struct ForceArgs {
@@ -249,44 +177,12 @@ __global__ void __launch_bounds__(AERO_THREADS) force_chunk_kernel(const ForceAr
       a[9 + c] += fabs(M[c]);
     }
   }
-  column_tree_reduce(a, sh, t, 1, AERO_THREADS);
+  column_tree_reduce<AERO_NACC>(a, sh, t, 1, AERO_THREADS);
   if (t == 0) {
     double* o = A.part + (size_t)blockIdx.x * AERO_NACC;
 #pragma unroll
     for (int k = 0; k < AERO_NACC; ++k) o[k] = a[k];
   }
-}
-
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-int chunk_cap(int n, int ngraph) { return (int)(((int64_t)n + AERO_ROWS - 1) / AERO_ROWS) + ngraph; }
-
-// scratch: [cnt int32 ngraph][coff int32 ngraph + 1][scan scratch][partials double cap * width]
-struct Scratch {
-  int32_t *cnt, *coff, *scan;
-  double* part;
-  size_t bytes;
-};
-Scratch carve(void* base, int n, int ngraph, int width) {
-  Scratch s;
-  char* p = reinterpret_cast<char*>(base);
-  size_t o = 0;
-  s.cnt = reinterpret_cast<int32_t*>(p + o);
-  o += up16(sizeof(int32_t) * (size_t)ngraph);
-  s.coff = reinterpret_cast<int32_t*>(p + o);
-  o += up16(sizeof(int32_t) * ((size_t)ngraph + 1));
-  s.scan = reinterpret_cast<int32_t*>(p + o);
-  o += up16(agn_scan_temp_bytes(ngraph));
-  s.part = reinterpret_cast<double*>(p + o);
-  o += up16(sizeof(double) * (size_t)chunk_cap(n, ngraph) * width);
-  s.bytes = o;
-  return s;
-}
-
-// per-graph chunk counts and their exclusive scan (coff[ngraph] = the total)
-int plan_chunks(const Scratch& s, int n, int ngraph, const int32_t* gptr, hipStream_t st) {
-  hipLaunchKernelGGL(chunk_count_kernel, dim3((ngraph + 255) / 256), dim3(256), 0, st, n, ngraph, gptr, s.cnt);
-  return agn_exclusive_scan_i32(s.cnt, s.coff, ngraph, s.coff + ngraph, s.scan, st);
 }
 
 }  // namespace

@@ -601,6 +601,67 @@ int agn_aero_forces(int dtype, int n, int dim, const void* pressure, const void*
                     double length_scale, double* area_out, const double* center, const int32_t* gptr, int ngraph,
                     double* out, void* scratch, void* stream);
 
+/* ---- 3-D surface evaluation from a face list (csrc/surface.hip).
+ * Replaces (reference file:line): inference.py:310-320 (the three VTK filters of the Ahmed-body branch:
+ * compute_normals(cell_normals=True), compute_cell_sizes(area=True), point_data_to_cell_data) followed by
+ * utils.py:385-448 (calculate_aero_coefficients_3d); utils.py:75-81 and :111-117 (the readers' graph:
+ * extract_all_edges + to_undirected(edge_index, num_nodes=N)).
+ *
+ * Face list: ncell cells over n points. CSR: offsets int64 [ncell + 1], conn int64 [nconn], cell c holds
+ * conn[offsets[c] .. offsets[c + 1]); regular: offsets == NULL, conn is [ncell][k]. nconn is the length of
+ * conn (slices are clamped to it). Node ids are global (a collated batch carries its node offsets) and
+ * must lie in [0, n): the caller validates them (torch.ops.aerognn.surface_forces and
+ * aerognn.surface.edges_from_faces do); the kernels clamp what they use as an address. The input must be
+ * consistently wound: VTK's consistent_normals traversal is not reproduced.
+ *
+ * agn_surface_forces: one pass over the cells. pos [n][3] (row stride pos_ld >= 3) of pos_dtype AGN_F32 or
+ *   AGN_F64, widened exactly; all geometry in fp64, every operation rounded once, nothing fused. Per cell
+ *   with points p_0 .. p_{m-1} in connectivity order:
+ *     d_i = p_i - p_0;  c_i = d_i x d_{i+1}, i = 1 .. m-2 (each component two products, one difference)
+ *     area = sum_i 0.5 * sqrt(c_i . c_i), ascending i, the dot product added left to right
+ *            (vtkCellSizeFilter's fan triangulation)
+ *     S = sum_i c_i, ascending i;  normal = S / |S| by three divisions, (0, 0, 0) when |S| == 0
+ *            (the direction of vtkPolygon::ComputeNormal)
+ *   m < 3: area 0 and a zero normal. pos == NULL skips the geometry (area 0, zero normal; area_out and
+ *   normal_out must be NULL): the point-to-cell means alone.
+ *   Fields: nset in 0..4 point-field sets fields[s] [n][4] (pressure, tau_x, tau_y, tau_z; row stride
+ *   field_ld[s] >= 4) of field_dtype AGN_F32 or AGN_F64; fields and field_ld are host arrays of nset
+ *   entries, read at the call. With mean, std [4] of the field dtype (both or neither) the point value is
+ *   v * std rounded, then + mean rounded (inference.py:77-82; the agn_eval_sums rule). The cell value is
+ *   sum_i w * v_i, w = 1.0 / m, in fp64 in ascending connectivity order, rounded once to the field dtype
+ *   (as vtkPointDataToCellData stores it); m == 0 gives 0. Per cell and set, the element rule of
+ *   agn_aero_forces with given areas: the normal rounded to the field dtype (VTK stores Normals as
+ *   float), pn = p_cell * normal rounded once in the field dtype, F = pn * area - tau_cell * area in fp64.
+ *   out [ngraph][nset][2][3] doubles: sum F and sum |F| per component, over the cell ranges
+ *   cgptr int32 [ngraph + 1] (ascending, clamped to [0, ncell]), by the two-stage reduction of
+ *   agn_aero_forces (agn_aero_chunk_rows() cells per chunk, chunks laid out from each graph's first cell,
+ *   the same element-to-thread map and trees). out[g][s] is BITWISE rows 0 and 2 of agn_aero_forces on the
+ *   cell arrays this entry emits (areas = area_out, normals = normal_out rounded to the field dtype,
+ *   pressure and shear from cell_out, gptr = cgptr, no pos); graph g of a batch is bitwise graph g alone;
+ *   two calls give identical bytes.
+ *   Optional outputs (stored when not NULL): area_out double [ncell], normal_out double [ncell][3]
+ *   (unrounded), cell_out [nset][ncell][4] of the field dtype. nset == 0 is geometry only (out unused).
+ *   scratch: agn_surface_forces_temp_bytes(ncell, ngraph, nset) bytes, 16-B aligned.
+ * agn_face_edges: for every cell side (v_i, v_{(i+1) mod m}) the keys u * n + v and v * n + u (m == 2: one
+ *   side; m < 2: none), sorted with agn_radix_sort_u64, run-flagged, scanned with agn_exclusive_scan_i32
+ *   and compacted: out int64 rows 0 and 1 (row stride out_ld >= 2 * nconn, the bound known before the
+ *   pass) hold the E directed edges ascending by (row, col) without duplicates, the coalesced order
+ *   to_undirected returns; a repeated vertex gives one self-loop. *ecount (device int32) = E.
+ *   2 * nconn must fit an int. scratch: agn_face_edges_temp_bytes(nconn) bytes, 16-B aligned.
+ * Errors: AGN_E_ARG (null pointer, negative count), AGN_E_DTYPE (anything but AGN_F32 / AGN_F64),
+ * AGN_E_SHAPE (nset outside 0..4, pos_ld < 3, field_ld < 4, mean without std, ncell * k > nconn, points
+ * named but n == 0, out_ld < 2 * nconn, 2 * nconn > INT32_MAX). ncell == 0 returns 0 without a launch
+ * (agn_face_edges then writes *ecount = 0). */
+size_t agn_surface_forces_temp_bytes(int ncell, int ngraph, int nset);
+int agn_surface_forces(int pos_dtype, int n, const void* pos, int pos_ld, int ncell, const int64_t* offsets,
+                       const int64_t* conn, int64_t nconn, int k, int field_dtype, int nset, const void* const* fields,
+                       const int* field_ld, const void* mean, const void* std, const int32_t* cgptr, int ngraph,
+                       double* out, double* area_out, double* normal_out, void* cell_out, void* scratch,
+                       void* stream);
+size_t agn_face_edges_temp_bytes(int64_t nconn);
+int agn_face_edges(int n, int ncell, const int64_t* offsets, const int64_t* conn, int64_t nconn, int k, int64_t* out,
+                   int64_t out_ld, int32_t* ecount, void* scratch, void* stream);
+
 /* ---- the training tail on the device: fused MSE loss + gradient, multi-tensor Adam.
  * Replaces (reference file:line): utils.py:191-192,195 (loss_fn(pred, batch.y) with nn.MSELoss, the
  * first step of loss.backward(), total_loss += loss.item()) and aerognn.dist.mse_sum_loss;

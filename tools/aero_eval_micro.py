@@ -4,7 +4,12 @@ device (the reference's own expressions of inference.py:76-126, :337-350 and uti
 per-edge Python loop of utils.py:516-520 replaced by index_add_), and against agn_col_stats and
 agn_segment_sum as the bandwidth yardsticks of the same machine.
 
-  python tools/aero_eval_micro.py [--n 1000] [--iters 20]
+  python tools/aero_eval_micro.py [--n 1000] [--iters 20] [--surface-only]
+
+The last rows are the 3-D surface passes (agn_surface_forces with two field sets and the geometry inline,
+agn_face_edges) on ellipsoid(n, n) with meshgen.lattice_faces, beside the same quantities from torch
+operators (gathers + linalg.cross for the forces, torch.unique for the edges); --surface-only runs
+those alone.
 
 Graph: an n x n triangulated grid (6 neighbours per interior node) with 2-D positions, edges in
 (sender, receiver) order as to_undirected leaves them. Per pass: ms per call (HIP events on torch's
@@ -86,11 +91,88 @@ def torch_forces(pos, ei, normals, pressure, shear):
     return torch.cat([F.sum(0), M.sum().reshape(1)])
 
 
+def torch_surface(pos, tri, fields, mean, std):
+    """inference.py:310-320 + utils.py:385-448 for triangles, composed from torch operators: cell areas
+    and normals in fp64, point-to-cell means, F = p n A - tau A summed per set."""
+    p = pos.double()
+    p0 = p[tri[:, 0]]
+    c = torch.linalg.cross(p[tri[:, 1]] - p0, p[tri[:, 2]] - p0)
+    ln = torch.linalg.norm(c, dim=1, keepdim=True)
+    area, nrm = 0.5 * ln, (c / ln).float()
+    out = []
+    for f in fields:
+        cell = (f * std + mean)[tri].double().mean(1).float()
+        out.append(((cell[:, :1] * nrm).double() * area - cell[:, 1:].double() * area).sum(0))
+    return torch.stack(out)
+
+
+def torch_edges(tri, n):
+    """extract_all_edges + to_undirected from torch operators: both directions of every side, unique keys."""
+    u = torch.cat([tri[:, 0], tri[:, 1], tri[:, 2]])
+    v = torch.cat([tri[:, 1], tri[:, 2], tri[:, 0]])
+    key = torch.unique(torch.cat([u * n + v, v * n + u]))
+    return torch.stack([key // n, key % n])
+
+
+def surface_rows(report, n, iters):
+    """agn_surface_forces (two field sets, geometry inline) and agn_face_edges on ellipsoid(n, n) with its
+    lattice_faces (n = 1000: 1 M points, about 2 M triangles), beside the torch compositions."""
+    from aerognn import surface
+    from aerognn.meshgen import ellipsoid, lattice_faces
+    pos = torch.from_numpy(ellipsoid(n, n, unique_x=False)["pos"]).to(dev)
+    tri = torch.from_numpy(lattice_faces(n, n)).to(dev)
+    N, C = pos.shape[0], tri.shape[0]
+    torch.manual_seed(1)
+    y = torch.randn(N, 4, device=dev)
+    pred = y + 0.1 * torch.randn(N, 4, device=dev)
+    mean = torch.tensor([1e5, 3.0, -2.0, 1.5], device=dev)
+    std = torch.tensor([3e4, 50.0, 40.0, 20.0], device=dev)
+    gptr = torch.tensor([0, C], dtype=torch.int32, device=dev)
+    print(f"surface: N={N} cells={C}", flush=True)
+    # what the pass must move: the face list once, every point's position and two field rows once
+    nbytes = C * 3 * 8 + N * (3 * 4 + 2 * 4 * 4)
+    op = lambda: torch.ops.aerognn.surface_forces(pos, None, tri, [y, pred], mean, std, gptr, False)  # noqa: E731
+    report("surface_forces (ours, op, ids checked)", timeit(op, iters), nbytes)
+    L = _lib.lib()
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    out = torch.zeros(1, 2, 2, 3, dtype=torch.float64, device=dev)
+    scratch = torch.empty(int(L.agn_surface_forces_temp_bytes(C, 1, 2)), dtype=torch.uint8, device=dev)
+    fptr = (ctypes.c_void_p * 2)(y.data_ptr(), pred.data_ptr())
+    fld = (ctypes.c_int * 2)(4, 4)
+
+    def kern():
+        rc = L.agn_surface_forces(_lib.F32, N, p(pos), 3, C, None, p(tri), tri.numel(), 3, _lib.F32, 2, fptr, fld, p(mean),
+                                  p(std), p(gptr), 1, p(out), None, None, None, p(scratch), st)
+        assert rc == 0, rc
+    report("surface_forces (ours, kernels only)", timeit(kern, iters), nbytes)
+    report("surface forces (torch composition)", timeit(lambda: torch_surface(pos, tri, [y, pred], mean, std), iters))
+    ours = op()[0][0]
+    ref = torch_surface(pos, tri, [y, pred], mean, std)
+    print("surface: ours vs torch composition, |diff| / S:", ((ours[:, 0] - ref).abs() / ours[:, 1]).tolist(), flush=True)
+    report("edges_from_faces (ours, count read back)", timeit(lambda: surface.edges_from_faces(tri, N), iters))
+    report("edges (torch composition, unique)", timeit(lambda: torch_edges(tri, N), iters))
+    assert torch.equal(surface.edges_from_faces(tri, N), torch_edges(tri, N))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1000)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--surface-only", action="store_true", help="only the 3-D surface rows")
     a = ap.parse_args()
+    res = {}
+
+    def report(name, ms, nbytes=None):
+        gbs = None if nbytes is None else nbytes / ms / 1e6
+        res[name] = {"ms": round(ms, 4), "bytes": nbytes, "GBps": None if gbs is None else round(gbs, 1)}
+        tail = "" if nbytes is None else f"  {nbytes / 1e6:9.1f} MB  {gbs:8.1f} GB/s"
+        print(f"{name:42s} {ms * 1e3:10.1f} us{tail}", flush=True)
+
+    if a.surface_only:
+        surface_rows(report, a.n, a.iters)
+        print(json.dumps(res), flush=True)
+        return
     pos_np, ei_np = grid_mesh(a.n)
     N, E, f, dim = pos_np.shape[0], ei_np.shape[1], 4, 2
     torch.manual_seed(0)
@@ -107,13 +189,7 @@ def main():
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     print(f"N={N} E={E} f={f} dim={dim} chunk rows={aero.CHUNK_ROWS}", flush=True)
-    res = {"N": N, "E": E}
-
-    def report(name, ms, nbytes=None):
-        gbs = None if nbytes is None else nbytes / ms / 1e6
-        res[name] = {"ms": round(ms, 4), "bytes": nbytes, "GBps": None if gbs is None else round(gbs, 1)}
-        tail = "" if nbytes is None else f"  {nbytes / 1e6:9.1f} MB  {gbs:8.1f} GB/s"
-        print(f"{name:34s} {ms * 1e3:10.1f} us{tail}", flush=True)
+    res.update({"N": N, "E": E})
 
     # ---- error sums
     report("eval_sums (ours, op)", timeit(lambda: torch.ops.aerognn.eval_sums(pred, y, mean, std, gptr), a.iters),
@@ -158,6 +234,8 @@ def main():
     report("agn_segment_sum [E, 128] bf16", timeit(
         lambda: L.agn_segment_sum(N, H, _lib.BF16, p(rowptr), None, p(g0), H, p(so2), H, 0, st), a.iters),
         (E + N) * H * 2 + N * 4)
+    del g0, so2
+    surface_rows(report, a.n, a.iters)
     print(json.dumps(res), flush=True)
 
 
