@@ -248,6 +248,7 @@ def lib():
             "agn_debug_dec32_launches": (C.c_long, []),
             "agn_debug_node32_bwd_launches": (C.c_long, []),
             "agn_debug_dec32_bwd_launches": (C.c_long, []),
+            "agn_debug_mlp_mode": (i32, [i32]),
             "agn_fault_status": (i32, [C.POINTER(i32), i32]),
             "agn_fault_status_async": (i32, [vp, vp]),
             "agn_debug_set_fault": (i32, [i32]),

@@ -1280,6 +1280,9 @@ bool bwd_ptrs_aligned(const agn_mlp_bwd_args* a) {
   return ok;
 }
 int g_opt_resident = 1;
+// agn_debug_mlp_mode: the I/O mode of the last general-kernel launch per direction ([0] forward,
+// [1] backward), -1 after a call that went to a resident kernel. Host-side only.
+int g_last_mode[2] = {-1, -1};
 bool res_fwd_ok(const agn_mlp_fwd_args* a, bool vec) {
   return g_opt_resident && vec && a->act_fn == AGN_ACT_RELU && a->dtype == AGN_BF16 && a->hidden == 128 && a->nlin <= RES_MAXL && a->nseg == 1 &&
          a->seg[0].kind == AGN_SEG_PLAIN && a->seg[0].k == 128 && a->out_dim == 128 && a->out_ld == 128 &&
@@ -1347,6 +1350,8 @@ int agn_pack(const agn_pack_desc* descs_device, int n, int max_threads, void* st
   return launch_status();
 }
 
+int agn_debug_mlp_mode(int backward) { return g_last_mode[backward ? 1 : 0]; }
+
 int agn_mlp_bwd_nwaves(int rows) {
   const int waves = (rows + 31) / 32;
   return (waves + WPB - 1) / WPB;
@@ -1385,6 +1390,7 @@ int agn_mlp_forward(const agn_mlp_fwd_args* a, void* stream) {
   }
   if (wide) mode = M_WIDE;  // (never in_full, never M_NIN: always the masked-I/O mode)
   const bool vec = mode == M_VEC;
+  g_last_mode[0] = -1;
   if (g_opt_resident && vec) {  // a processor layer's node MLP: resident weights, aggregation walked in
     int rc = 0;
     if (agn::node32_fwd_try(a, stream, &rc)) return rc;
@@ -1403,6 +1409,7 @@ int agn_mlp_forward(const agn_mlp_fwd_args* a, void* stream) {
     return launch_status();
   }
   dim3 grid(agn_mlp_bwd_nwaves(a->rows));
+  g_last_mode[0] = mode;
   AGN_DISPATCH(AGN_FWD_MODES);
   return launch_status();
 }
@@ -1438,6 +1445,7 @@ int agn_mlp_backward(const agn_mlp_bwd_args* a, void* stream) {
   }
   const bool vec = mode == M_VEC && !wide;
   agn_mlp_bwd_args* am = const_cast<agn_mlp_bwd_args*>(a);
+  g_last_mode[1] = -1;
   if (g_opt_resident && vec) {  // a processor layer's node MLP: resident weights
     int rc = 0, lr = 0;
     if (agn::node32_bwd_try(a, stream, &rc, &lr)) {
@@ -1461,6 +1469,7 @@ int agn_mlp_backward(const agn_mlp_bwd_args* a, void* stream) {
   dim3 grid(agn_mlp_bwd_nwaves(a->rows));
   am->ln_rows = (int)grid.x;
   if (wide) mode = M_WIDE;  // a wide dX that is wanted: the masked-I/O mode's WIDE instantiation
+  g_last_mode[1] = mode;
   AGN_DISPATCH(AGN_BWD_MODES);
   return launch_status();
 }

@@ -234,6 +234,12 @@ int agn_mlp_forward(const agn_mlp_fwd_args* a, void* stream);
 /* rows of ln_partial written by agn_mlp_backward (one per 256-row block) */
 int agn_mlp_bwd_nwaves(int rows);
 int agn_mlp_backward(const agn_mlp_bwd_args* a, void* stream);
+/* testing: which instantiation of the general MLP kernels the last agn_mlp_forward (backward = 0) or
+ * agn_mlp_backward (backward != 0) launched: 0 M_VEC (16-B row I/O everywhere), 1 M_GEN (masked
+ * 4-feature chunks), 2 M_NIN (one input of <= 16 features; forward only), 3 M_NOUT (<= 32 outputs,
+ * no LayerNorm), 4 M_WIDE (a segment wider than hidden); -1 if that call went to a resident kernel
+ * or no call has launched yet. Host-side state only (a call rejected before its launch leaves it). */
+int agn_debug_mlp_mode(int backward);
 /* out[c] = sum_w partial[w][c], c < n, fixed order (deterministic LN parameter grads) */
 int agn_reduce_partials(const float* partial, int nw, int n, float* out, void* stream);
 

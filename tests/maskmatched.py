@@ -24,9 +24,17 @@ def bf(t):
 
 
 def decode_tiled(t, rows, width=H):
-    """AGN_TILED [rows_pad, 128] 16-bit -> row-major [rows, 128] (aerognn.h: unit (i, h) of row c
-    holds features 16i+4h+{0..3}, 16i+8+4h+{0..3})."""
+    """AGN_TILED [rows_pad, 128] -> row-major [rows, 128] (aerognn.h). bf16 / fp16: unit (i, h) of row c
+    holds features 16i+4h+{0..3}, 16i+8+4h+{0..3}; fp32: 16 units per lane half-row, unit (i, h) of row c
+    holds features 8i+4h+{0..3}."""
     assert width == H
+    if t.dtype == torch.float32:
+        u = t.reshape(-1, 16, 2, 32, 4)  # [tile][i][h][c][4]
+        out = torch.empty(u.shape[0], 32, H, dtype=t.dtype, device=t.device)
+        for i in range(16):
+            for hh in range(2):
+                out[:, :, 8 * i + 4 * hh:8 * i + 4 * hh + 4] = u[:, i, hh]
+        return out.reshape(-1, H)[:rows]
     u = t.view(torch.int16).reshape(-1, 8, 2, 32, 8)  # [tile][i][h][c][8]
     out = torch.empty(u.shape[0], 32, H, dtype=torch.int16, device=t.device)
     for i in range(8):

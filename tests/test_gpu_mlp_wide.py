@@ -12,8 +12,8 @@ import os
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+from chainref import kink_free_rows, ref_chain, torch_16bit
 from golden_util import load, max_rel, params, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -35,43 +35,6 @@ def _gate(what, got, ref, tol):
     print(f"{what}: rel-L2 {r:.2e}, max-elem {mx:.2e} (gate {tol:.0e})")
     assert r <= tol and mx <= tol, (what, r, mx)
     return r
-
-
-def ref_chain(sd, x, act="relu", gy=None):
-    """The float64 formula of models/mlp.py:40-51 on the parameters `sd` (any dtype, upcast):
-    (y, pre-activations) or, with gy, (y, gx, {name: grad})."""
-    p = {k: v.detach().cpu().double().requires_grad_(gy is not None) for k, v in sd.items()}
-    x = x.detach().cpu().double().requires_grad_(gy is not None)
-    n = sum(1 for k in p if k.startswith("layers.") and k.endswith(".weight"))
-    h, pres = x, []
-    for l in range(n):
-        h = F.linear(h, p[f"layers.{l}.weight"], p[f"layers.{l}.bias"])
-        if l < n - 1:
-            pres.append(h)
-            h = getattr(F, act)(h)
-    if "layer_norm.weight" in p:
-        h = F.layer_norm(h, (h.shape[1],), p["layer_norm.weight"], p["layer_norm.bias"], 1e-5)
-    if gy is None:
-        return h.detach(), [t.detach() for t in pres]
-    h.backward(gy.detach().cpu().double())
-    return h.detach(), x.grad, {k: v.grad for k, v in p.items()}
-
-
-def kink_free_rows(sd, x, gen, act="relu", band=1e-5, rounds=8):
-    """tests/kinkfree.py's rule for one chain: rows with a float64 ReLU input within band * std of 0 are
-    re-drawn (a ReLU derivative jumps there, and two valid fp32 summation orders may take different
-    sides), until none is. Decided by the float64 formula alone, never by the kernels."""
-    if act != "relu":
-        return x
-    for _ in range(rounds):
-        _, pres = ref_chain(sd, x)
-        near = torch.zeros(x.shape[0], dtype=torch.bool)
-        for t in pres:
-            near |= (t.abs() < band * t.std()).any(1) if t.numel() > 1 else (t.abs() < band).any(1)
-        if not near.any():
-            return x
-        x[near] = torch.randn(int(near.sum()), x.shape[1], generator=gen, dtype=x.dtype)
-    raise AssertionError("rows not kink-free")
 
 
 def _run(model, x, gy, rows=None):
@@ -112,23 +75,6 @@ def test_golden_f64(name):
 Y16 = {torch.bfloat16: 7.5e-3, torch.float16: 1e-3}                     # 3 x measured (y)
 G16 = {(torch.float16, True): 2.3e-3, (torch.float16, False): 2.3e-3,  # 3 x measured (gradients)
        (torch.bfloat16, False): 1.7e-2, (torch.bfloat16, True): None}  # None: max(2e-2, 2 x torch's own bf16)
-
-
-def torch_16bit(sd, x, act, gy):
-    """torch's own evaluation of the chain in the 16-bit dtype on the CPU (the reference module's
-    arithmetic, mlp.py:40-51): (y, gx, {name: grad})."""
-    p = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
-    x = x.detach().clone().requires_grad_(True)
-    n = sum(1 for k in p if k.startswith("layers.") and k.endswith(".weight"))
-    h = x
-    for l in range(n):
-        h = F.linear(h, p[f"layers.{l}.weight"], p[f"layers.{l}.bias"])
-        if l < n - 1:
-            h = getattr(F, act)(h)
-    if "layer_norm.weight" in p:
-        h = F.layer_norm(h, (h.shape[1],), p["layer_norm.weight"], p["layer_norm.bias"], 1e-5)
-    h.backward(gy)
-    return h.detach(), x.grad, {k: v.grad for k, v in p.items()}
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
