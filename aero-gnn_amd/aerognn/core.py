@@ -665,6 +665,8 @@ class WGrad:
         """xidx: X is gathered, row r of the operand = X[xidx[r]] (int32, one entry per row of G)."""
         assert G.dtype == X.dtype and logical_rows(G) == (logical_rows(X) if xidx is None else xidx.numel())
         assert dw.dtype == torch.float32 and dw.stride(1) == 1
+        # stride(0) is the kernel's leading dimension: the columns of a row must be adjacent
+        assert (G.stride(1) == 1 or G.shape[1] == 1) and (X.stride(1) == 1 or X.shape[1] == 1)
         assert xidx is None or (xidx.dtype == torch.int32 and not is_tiled(X))
         self.items.append((G, X, dw, db, xidx))
 
