@@ -481,9 +481,18 @@ def edge_bwd_fused(*, rows, wpk, wtpk0, bias, ln_g, e, proj, src, dst, g, g2, de
     a2 goes through a scratch buffer instead of a second recompute on the recompute path (with a1 /
     stats, a2 and a3 stay in registers; bitwise the same outputs; not faster, and its slices leave L2:
     DESIGN.md §9 round 6)."""
+    return _fused_bwd("edge_bwd_fused", rows, wpk, bias, ln_g, g2.device, scratch, tag, cost,
+                      e=ptr(e), proj=ptr(proj), src=ptr(src), dst=ptr(dst), g=ptr(g), g2=ptr(g2), de=ptr(de), g0=ptr(g0),
+                      a1=ptr(a1), stats=ptr(stats), wtpk0=wtpk0)  # wtpk0: W_e^T packed (ChainSpec.wtpk()[0])
+
+
+def _fused_bwd(entry, rows, wpk, bias, ln_g, dev, scratch, tag, cost, **fields):
+    """One launch of a fused backward (the C-ABI entry point agn_<entry>, an EdgeBwdArgs) and its slab
+    reduction: the per-block dW / db slabs and LayerNorm partials, the scratch buffer (scratch None:
+    AEROGNN_EB_SCRATCH decides), the packed weights and biases and the stamps pointer are filled here,
+    `fields` are the entry point's own arguments; then the fault word is checked (or polled)."""
     import os
     lib = L.lib()
-    dev = g2.device
     H = 128
     nblk = int(lib.agn_edge_bwd_blocks(int(rows)))
     dwp = torch.empty(3 * nblk * H * H, dtype=torch.float32, device=dev)
@@ -499,18 +508,17 @@ def edge_bwd_fused(*, rows, wpk, wtpk0, bias, ln_g, e, proj, src, dst, g, g2, de
         a.wpk[i] = wpk[i]
         a.bias[i] = bias[i]
     a.ln_g = ln_g
-    a.e, a.proj, a.src, a.dst = ptr(e), ptr(proj), ptr(src), ptr(dst)
-    a.g, a.g2 = ptr(g), ptr(g2)
-    a.de, a.g0, a.dw_partial, a.db_partial, a.ln_partial = ptr(de), ptr(g0), ptr(dwp), ptr(dbp), ptr(lnp)
+    a.dw_partial, a.db_partial, a.ln_partial, a.scratch = ptr(dwp), ptr(dbp), ptr(lnp), ptr(scr)
     a.stamps = ptr(STAMPS)
-    a.a1, a.stats, a.scratch = ptr(a1), ptr(stats), ptr(scr)
-    a.wtpk0 = wtpk0  # W_e^T packed (ChainSpec.wtpk()[0])
+    for k, v in fields.items():
+        assert hasattr(L.EdgeBwdArgs, k), k  # (ctypes would take a misspelt field silently)
+        setattr(a, k, v)
     with timed(tag, cost):
-        check(lib.agn_edge_bwd_fused(C.byref(a), stream()), "edge_bwd_fused")
+        check(getattr(lib, "agn_" + entry)(C.byref(a), stream()), entry)
     if CHECK_FAULTS:  # tests / debug runs: a bounded ring wait that gave up is an error, not wrong dW
         f = L.fault_status(reset=True)
         if f:
-            raise L.AeroGNNError(f"agn_edge_bwd_fused: device fault word {f:#x} (LDS ring wait timed out; dW invalid)")
+            raise L.AeroGNNError(f"agn_{entry}: device fault word {f:#x} (LDS ring wait timed out; dW invalid)")
     else:
         _poll_faults()
     return _reduce_slabs(rows, dwp, dbp, lnp, nblk, dev)
@@ -545,35 +553,8 @@ def encoder_bwd_fused(*, rows, wpk, bias, ln_g, x, xidx, g, g0, tag=None, cost=N
     """agn_encoder_bwd_fused: (dW1..dW3, db1..db3, LayerNorm partials, nblk) of an encoder chain, and
     G0 into g0 ([rows, 128] row-major) for dW0 / db0; x [n, k] bf16 (rows gathered by xidx, int32,
     when given)."""
-    lib = L.lib()
-    dev = g.device
-    H = 128
-    nblk = int(lib.agn_edge_bwd_blocks(int(rows)))
-    dwp = torch.empty(3 * nblk * H * H, dtype=torch.float32, device=dev)
-    dbp = torch.empty(3 * nblk * H, dtype=torch.float32, device=dev)
-    lnp = torch.empty(nblk, 2 * H, dtype=torch.float32, device=dev)
-    import os
-    scr = (torch.empty(int(lib.agn_edge_bwd_scratch_bytes(nblk)), dtype=torch.uint8, device=dev)
-           if os.environ.get("AEROGNN_EB_SCRATCH", "0") == "1" else None)
-    a = L.EdgeBwdArgs()
-    a.rows, a.nblk = int(rows), nblk
-    for i in range(4):
-        a.wpk[i] = wpk[i]
-        a.bias[i] = bias[i]
-    a.ln_g = ln_g
-    a.e, a.src, a.g, a.g0 = ptr(x), ptr(xidx), ptr(g), ptr(g0)
-    a.dw_partial, a.db_partial, a.ln_partial, a.scratch = ptr(dwp), ptr(dbp), ptr(lnp), ptr(scr)
-    a.xk, a.xld = int(x.shape[1]), int(x.stride(0))
-    a.stamps = ptr(STAMPS)
-    with timed(tag, cost):
-        check(lib.agn_encoder_bwd_fused(C.byref(a), stream()), "encoder_bwd_fused")
-    if CHECK_FAULTS:
-        f = L.fault_status(reset=True)
-        if f:
-            raise L.AeroGNNError(f"agn_encoder_bwd_fused: device fault word {f:#x} (LDS ring wait timed out; dW invalid)")
-    else:
-        _poll_faults()
-    return _reduce_slabs(rows, dwp, dbp, lnp, nblk, dev)
+    return _fused_bwd("encoder_bwd_fused", rows, wpk, bias, ln_g, g.device, None, tag, cost,
+                      e=ptr(x), src=ptr(xidx), g=ptr(g), g0=ptr(g0), xk=int(x.shape[1]), xld=int(x.stride(0)))
 
 
 def reduce_partials(partial, nw, n, out):

@@ -22,25 +22,36 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from ._lib import check, ptr
 from . import core as _core
-from .core import (Pack, WGrad, alg8d_edge, alg8d_node, with_alg, edge_bwd_fused, fused_edge_train_ok, bwd_nblocks,
-                   edge32_ok, edge_saves_ok, edge_agg_ok, edge_forward,
-                   cost_edge_bwd_fused,
-                   proj_kernel_ok, proj_forward, proj_backward, wgrad_dpd_ok, wgrad_segsum, tiled_empty, relu_mask_empty, colsum_rows, cost_edge_bwd, cost_edge_bwd_cat, cost_edge_fwd,
-                   cost_edge_fwd_cat, cost_node_bwd, cost_node_fwd, cost_proj, cost_wec_bwd, cost_wec_fwd, dt_code,
-                   timed, gather_rows, mlp_backward, mlp_forward, require_device,
-                   scatter_rows, segment_max, segment_max_backward, segment_sum, segment_sum2, stream)
+from ._lib import check, ptr
+from .core import (Pack, WGrad, alg8d_edge, alg8d_node, bwd_nblocks, colsum_rows, cost_edge_bwd, cost_edge_bwd_cat,
+                   cost_edge_bwd_fused, cost_edge_fwd, cost_edge_fwd_cat, cost_node_bwd, cost_node_fwd, cost_proj,
+                   cost_wec_bwd, cost_wec_fwd, dt_code, edge32_ok, edge_agg_ok, edge_bwd_fused, edge_forward,
+                   edge_saves_ok, fused_edge_train_ok, gather_rows, mlp_backward, mlp_forward, proj_backward,
+                   proj_forward, proj_kernel_ok, relu_mask_empty, require_device, scatter_rows, segment_max,
+                   segment_max_backward, segment_sum, segment_sum2, stream, tiled_empty, timed, wgrad_dpd_ok,
+                   wgrad_segsum, with_alg)
 
 
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _ln_grads(partial, nblk, M, dtype):
+def _plain(t, k=None):
+    """The mlp_forward input segment of k columns (default: all) of t's rows."""
+    return (L.SEG_PLAIN, t.shape[1] if k is None else k, t.stride(0), t, None, None)
+
+
+def _gather(t, idx, k=None):
+    """The segment of the rows t[idx] (idx int32), gathered by the kernel's input loads."""
+    return (L.SEG_GATHER, t.shape[1] if k is None else k, t.stride(0), t, idx, None)
+
+
+def _ln_grads(partial, nblk, M):
+    """[dgamma, dbeta] (fp32) from a backward kernel's nblk rows of LayerNorm partials."""
     out = torch.empty(2 * M, dtype=torch.float32, device=partial.device)
     colsum_rows(partial, nblk, 2 * M, out)
-    return out[:M].to(dtype), out[M:].to(dtype)
+    return [out[:M], out[M:]]
 
 
 # --------------------------------------------------------------------------- chain specs
@@ -138,11 +149,17 @@ def _alloc_gpre(spec, rows, dtype, dev, rowmajor=()):
     return out
 
 
+def _to_param_dtypes(spec, grads):
+    """fp32 gradients in spec.params() order, each cast to its parameter's dtype (one rounding)."""
+    return [g if g.dtype == p.dtype else g.to(p.dtype) for g, p in zip(grads, spec.params())]
+
+
 def _chain_param_grads(spec, gpre, inputs0, acts, lnp_partial, nblk, wg=None, tag="wgrad_enc"):
     """Grads (in spec.params() order) from stored pre-activation grads.
 
-    Queues the dW/db products on `wg` (a core.WGrad); the returned fp32 tensors are filled
-    when wg.run() executes (run here if no batch object is passed in).
+    Queues the dW/db products on `wg` (a core.WGrad). Without one they run here and the grads come
+    back in the parameters' dtypes. With the caller's batch object the fp32 tensors come back as they
+    are, filled when the caller's wg.run() executes: it casts them after that (_to_param_dtypes).
     """
     own = wg is None
     wg = wg or WGrad(tag)
@@ -162,16 +179,59 @@ def _chain_param_grads(spec, gpre, inputs0, acts, lnp_partial, nblk, wg=None, ta
                 k0 += X.shape[1]
         else:
             wg.add(G, inputs0 if l == 0 else acts[l - 1], dw, db)
-        grads.append((dw, w.dtype))
+        grads.append(dw)
         if b is not None:
-            grads.append((db, b.dtype))
+            grads.append(db)
     if own:
         wg.run()
-    out = [g if g.dtype == dt else g.to(dt) for g, dt in grads]
     if spec.ln is not None:
-        g, bb = _ln_grads(lnp_partial, nblk, spec.out_dim, spec.ln[0].dtype)
-        out += [g, bb]
-    return out
+        grads += _ln_grads(lnp_partial, nblk, spec.out_dim)
+    return _to_param_dtypes(spec, grads) if own else grads
+
+
+def _chain_backward(spec, rows, saves, g, din, *, g2=None, gidx=None, rowmajor=(), tag=None, cost=None):
+    """One agn_mlp_backward launch over a chain's `rows` rows, from the forward's saves (acts, hpre,
+    stats) and the output gradient g (+ g2[gidx]; g None reads as zero); din as mlp_backward takes it.
+    Returns (gpre, ln_partial, nblk): the pre-activation gradients (_alloc_gpre), the LayerNorm
+    partials (None without a LayerNorm) and the number of partial rows the kernel wrote."""
+    acts, hpre, stats = saves
+    like = g if g is not None else g2
+    gpre = _alloc_gpre(spec, rows, like.dtype, like.device, rowmajor)
+    part = None
+    if spec.ln is not None:
+        part = torch.empty(bwd_nblocks(rows), 2 * spec.out_dim, dtype=torch.float32, device=like.device)
+    nblk = mlp_backward(rows=rows, dtype=like.dtype, hidden=spec.hidden, nlin=spec.nlin, act_fn=spec.act,
+                        out_dim=spec.out_dim, in_dim=spec.in_dim, wtpk=spec.wtpk(), acts=acts or [], g=g, g2=g2,
+                        gidx=gidx, gpre=gpre, ln_g=spec.lnp()[0] if spec.ln is not None else None, hpre=hpre,
+                        stats=stats, din=din, ln_partial=part, tag=tag, cost=cost)
+    return gpre, part, nblk
+
+
+def _g0_grads(spec, g0, x, tag, xidx=None):
+    """A fused backward leaves the first Linear to agn_wgrad: dW0 = G0^T x and db0 (None for a bias-free
+    first Linear), fp32. xidx: the operand is x[xidx] (MLPFn on gathered rows, the edge encoder)."""
+    w0, b0 = spec.linears[0]
+    dw0 = torch.empty(w0.shape, dtype=torch.float32, device=g0.device)
+    db0 = torch.empty(w0.shape[0], dtype=torch.float32, device=g0.device) if b0 is not None else None
+    wg = WGrad(tag)
+    wg.add(g0, x, dw0, db0, xidx=xidx)
+    wg.run()
+    return dw0, db0
+
+
+def _fused_chain_grads(spec, dw0, db0, dW13, db13, ln_partial, nblk):
+    """Grads in spec.params() order from a fused backward (edge_bwd_fused / encoder_bwd_fused): dW0 / db0
+    from _g0_grads (db0 None: a bias-free first Linear, the sum-trick's edge_lin), dW1..dW3 / db1..db3
+    as the kernel reduced them, the LayerNorm gradients from its partials. Everything is formed in fp32
+    and cast once to its parameter's dtype at the end; where in the sequence that cast happens does not
+    change the value (one rounding of the same fp32 number), so one order serves every caller."""
+    grads = [dw0] + ([db0] if db0 is not None else [])
+    for l in range(3):
+        grads.append(dW13[l])
+        if spec.linears[l + 1][1] is not None:
+            grads.append(db13[l])
+    grads += _ln_grads(ln_partial, nblk, spec.out_dim)
+    return _to_param_dtypes(spec, grads)
 
 
 # --------------------------------------------------------------------------- MLP
@@ -210,9 +270,9 @@ class MLPFn(torch.autograd.Function):
         idx = None
         if rows is not None:
             idx = rows.to(torch.int32).contiguous()
-            segs = [(L.SEG_GATHER, k, x.stride(0), x[:, k0:], idx, None) for k0, k in ks]
+            segs = [_gather(x[:, k0:], idx, k) for k0, k in ks]
         else:
-            segs = [(L.SEG_PLAIN, k, x.stride(0), x[:, k0:], None, None) for k0, k in ks]
+            segs = [_plain(x[:, k0:], k) for k0, k in ks]
         mlp_forward(rows=nrow, dtype=dt, hidden=spec.hidden, nlin=spec.nlin, act_fn=spec.act, out_dim=spec.out_dim,
                     segs=segs, wpk=spec.wpk(), bias=spec.biases(), ln=spec.lnp(), out=out,
                     acts=acts, hpre=hpre, stats=stats)
@@ -237,32 +297,13 @@ class MLPFn(torch.autograd.Function):
             dW13, db13, part, nblk = _core.encoder_bwd_fused(
                 rows=rows, wpk=spec.wpk(), bias=spec.biases(), ln_g=spec.lnp()[0], x=x, xidx=ctx.idx, g=gy, g0=g0,
                 tag="enc_bwd", cost=(0.0, 2.0 * rows * H * H * 9, rows * (3 * H * s_el + 2 * x.shape[1] + 4)))
-            w0, b0 = spec.linears[0]
-            dw0 = torch.empty(w0.shape, dtype=torch.float32, device=x.device)
-            db0 = torch.empty(H, dtype=torch.float32, device=x.device) if b0 is not None else None
-            wg = WGrad("wgrad_enc")
-            wg.add(g0, x, dw0, db0, xidx=ctx.idx)
-            wg.run()
-            grads = [dw0] + ([db0] if b0 is not None else [])
-            for l in range(3):
-                w, b = spec.linears[l + 1]
-                grads.append(dW13[l])
-                if b is not None:
-                    grads.append(db13[l])
-            grads += list(_ln_grads(part, nblk, H, torch.float32))
-            params = spec.params()
-            grads = [gr if gr.dtype == p.dtype else gr.to(p.dtype) for gr, p in zip(grads, params)]
-            return (None, None, None, None, *grads)
-        gpre = _alloc_gpre(spec, rows, dt, x.device)
+            dw0, db0 = _g0_grads(spec, g0, x, "wgrad_enc", xidx=ctx.idx)
+            return (None, None, None, None, *_fused_chain_grads(spec, dw0, db0, dW13, db13, part, nblk))
         ks = _ksegs(x, spec.hidden)
         need_dx = ctx.needs_input_grad[0]
         dparts = [torch.empty(rows, k, dtype=dt, device=x.device) if need_dx else None for _, k in ks]
-        nblk = bwd_nblocks(rows)
-        part = torch.empty(nblk, 2 * spec.out_dim, dtype=torch.float32, device=x.device) if spec.ln else None
-        nblk = mlp_backward(rows=rows, dtype=dt, hidden=spec.hidden, nlin=spec.nlin, act_fn=spec.act, out_dim=spec.out_dim,
-                            in_dim=spec.in_dim, wtpk=spec.wtpk(), acts=ctx.acts or [], g=gy, gpre=gpre,
-                            ln_g=spec.lnp()[0] if spec.ln else None, hpre=ctx.hpre, stats=ctx.stats,
-                            din=[(k, d, False) for (_, k), d in zip(ks, dparts)], ln_partial=part)
+        gpre, part, nblk = _chain_backward(spec, rows, (ctx.acts, ctx.hpre, ctx.stats), gy,
+                                           [(k, d, False) for (_, k), d in zip(ks, dparts)])
         dx = None
         if need_dx:
             dx = dparts[0] if len(dparts) == 1 else torch.cat(dparts, 1)
@@ -407,6 +448,12 @@ class LayerSpec:
                                       H, self.pack, "e", act=em.activation_fn)
             # (EdgeBlockSum's chain is ReLU whatever activation_fn says: mgnLayer.py:81)
         self.H = H
+        self._check_widths()
+
+    def _check_widths(self, edge_in=None):
+        """The kernels' width contract: hidden 32/64/128 and node_dim == edge_dim == hidden_dim.
+        edge_in: the concat edge chain's input width where the caller knows it (from_gmp: 3 H)."""
+        H = self.H
         if H not in (32, 64, 128):
             raise NotImplementedError(f"aerognn kernels support hidden 32/64/128, got {H}")
         for c in (self.edge, self.node):
@@ -414,7 +461,7 @@ class LayerSpec:
                 c.check_hidden()
                 if c.out_dim != H:
                     raise NotImplementedError("aerognn GMP kernels need node_dim == edge_dim == hidden_dim")
-        if self.node is not None and self.node.in_dim != 2 * H:
+        if (self.node is not None and self.node.in_dim != 2 * H) or (edge_in is not None and self.edge.in_dim != edge_in):
             raise NotImplementedError("aerognn GMP kernels need node_dim == edge_dim == hidden_dim")
 
     @classmethod
@@ -433,20 +480,12 @@ class LayerSpec:
             raise NotImplementedError("aerognn GMP kernels implement ReLU / SiLU / GELU / Tanh MLPs")
         e0, e2, eln = gmp.edge_mlp[0], gmp.edge_mlp[2], gmp.edge_mlp[3]
         n0, n2, nln = gmp.node_mlp[0], gmp.node_mlp[2], gmp.node_mlp[3]
-        H = e0.weight.shape[0]
-        if H not in (32, 64, 128):
-            raise NotImplementedError(f"aerognn kernels support hidden 32/64/128, got {H}")
+        self.H = H = e0.weight.shape[0]
         self.edge = ChainSpec([(e0.weight, e0.bias), (e2.weight, e2.bias)], (eln.weight, eln.bias), H, self.pack, "e",
                               act=ea)
         self.node = ChainSpec([(n0.weight, n0.bias), (n2.weight, n2.bias)], (nln.weight, nln.bias), H, self.pack, "n",
                               act=na)
-        self.H = H
-        for c in (self.edge, self.node):
-            c.check_hidden()
-            if c.out_dim != H:
-                raise NotImplementedError("aerognn GMP kernels need node_dim == edge_dim == hidden_dim")
-        if self.node.in_dim != 2 * H or self.edge.in_dim != 3 * H:
-            raise NotImplementedError("aerognn GMP kernels need node_dim == edge_dim == hidden_dim")
+        self._check_widths(edge_in=3 * H)
         return self
 
     def edge_params(self):
@@ -462,6 +501,90 @@ class LayerSpec:
 
     def params(self):
         return self.edge_params() + self.node_params()
+
+
+# --------------------------------------------------------------------------- shared block steps
+def _walk(aggregation, e, rowptr, store, H):
+    """The node kernel's SUM / MEAN input segment (mgnLayer.py:144-146, trial1.py:68): it walks each
+    receiver's CSC range of e in edge order (torch_scatter's fp32 order) and, given `store`, also
+    writes the sums / means there for the weight gradient."""
+    return (L.SEG_MEAN if aggregation == "mean" else L.SEG_SUM, H, e.stride(0), e, rowptr, store)
+
+
+def _node_forward(ns, x, aseg, out, saves, *, resid, tag=None, cost=None):
+    """The node chain on [x | aseg]; aseg is a _walk over e' or the receiver sums as a _plain segment.
+    resid: out = x + chain (a whole layer) or the chain alone (NodeBlockFn)."""
+    acts, hpre, stats = saves
+    H = ns.hidden
+    mlp_forward(rows=x.shape[0], dtype=x.dtype, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H,
+                segs=[_plain(x, H), aseg], wpk=ns.wpk(), bias=ns.biases(), ln=ns.lnp(), resid=x if resid else None,
+                out=out, acts=acts, hpre=hpre, stats=stats, tag=tag, cost=cost)
+
+
+def _node_backward(ns, x, saves, g, *, resid, mean_ptr=None, tag=None, cost=None):
+    """The node chain's backward: (dx, dagg, (gpre, ln_partial, nblk)). resid as in _node_forward (dx then
+    includes g). mean_ptr: the level's rowptr where scatter_mean's / max(deg, 1) is applied to dagg here
+    (NodeBlockFn folds it into its gather to the edges instead)."""
+    N, H = x.shape[0], ns.hidden
+    dx = torch.empty_like(x)
+    dagg = torch.empty(N, H, dtype=x.dtype, device=x.device)
+    chain = _chain_backward(ns, N, saves, g, [(H, dx, resid), (H, dagg, False)], tag=tag, cost=cost)
+    if mean_ptr is not None:
+        dagg = gather_rows(N, H, None, dagg, torch.empty_like(dagg), cnt_ptr=mean_ptr)
+    return dx, dagg, chain
+
+
+def _proj_forward(spec, x, *, kernel, tag=None, cost=None):
+    """The sum-trick's node projections P = x [W_s; W_d]^T + [0; b] ([N, 2H]): the persistent projection
+    kernel where it applies, else a one-Linear agn_mlp_forward. kernel=False and no tag: EdgeBlockFn,
+    which has always run the general kernel untagged (kept; DESIGN.md "host layer")."""
+    N, H = x.shape[0], spec.H
+    P = torch.empty(N, 2 * H, dtype=x.dtype, device=x.device)
+    if kernel and proj_kernel_ok(x, H):
+        proj_forward(N, x, spec.pack["proj"], spec.pack["proj_b"], P, tag=tag, cost=cost)
+    else:
+        mlp_forward(rows=N, dtype=x.dtype, hidden=H, nlin=1, out_dim=2 * H, segs=[_plain(x)],
+                    wpk=[spec.pack["proj"]], bias=[spec.pack["proj_b"]], out=P, tag=tag, cost=cost)
+    return P
+
+
+def _proj_backward(spec, lv, x, g0, wg, *, dx=None, dwe=None, e=None):
+    """Backward of h0 = e W_e^T + P_s[src] + P_d[dst] past G0: dP_s / dP_d by sender / receiver groups
+    (fixed order), dx (+)= [dP_s | dP_d] projT, and dW_s, dW_d, db_d queued on `wg` (fp32, filled by the
+    caller's wg.run()). Returns (dx, dws, dwd, dbd).
+    dwe (with e; GMPFn's fused path, which has no other dW_e launch to share): dP_d and dW_e = G0^T e
+    walk G0's rows in the same (CSC) order, so one agn_wgrad_segsum pass forms both here, bitwise the two
+    launches it replaces ("dP_d inside the dW_e pass").
+    dx None: EdgeBlockFn, which has no node gradient to add to and has always run the general kernel
+    into a zeroed dx (kept; DESIGN.md "host layer"); GMPFn passes the node block's dx."""
+    N, H = x.shape[0], spec.H
+    dt, dev = x.dtype, x.device
+    dPs = segment_sum(N, H, lv.rowptr_src, lv.perm_src, g0, torch.empty(N, H, dtype=dt, device=dev))
+    dPd = torch.empty(N, H, dtype=dt, device=dev)
+    if dwe is not None:
+        wgrad_segsum(g0, e, dwe, lv.rowptr, lv.dst, dPd)
+    else:
+        segment_sum(N, H, lv.rowptr, None, g0, dPd)
+    if dx is not None and proj_kernel_ok(dx, H):
+        s_el = dx.element_size()
+        proj_backward(N, dPs, dPd, spec.pack["projT"], dx, tag="proj_bwd",
+                      cost=with_alg(alg8d_node(N, H, s_el, bwd=True), (4 * N * H * s_el, 4.0 * N * H * H)))
+    else:
+        resid, dx = dx, (torch.zeros_like(x) if dx is None else dx)
+        mlp_forward(rows=N, dtype=dt, hidden=H, nlin=1, out_dim=H, segs=[_plain(dPs), _plain(dPd)],
+                    wpk=[spec.pack["projT"]], bias=[None], resid=resid, out=dx)
+    dws = torch.empty(H, x.shape[1], dtype=torch.float32, device=dev)
+    dwd = torch.empty(H, x.shape[1], dtype=torch.float32, device=dev)
+    dbd = torch.empty(H, dtype=torch.float32, device=dev)
+    wg.add(dPs, x, dws)
+    wg.add(dPd, x, dwd, dbd)
+    return dx, dws, dwd, dbd
+
+
+def _splice_proj(spec, eg, dws, dwd, dbd):
+    """Edge gradients in LayerSpec.edge_params() order: the projection's after dW_e (after wg.run())."""
+    eb = spec.eb
+    return [eg[0], dws.to(eb.src_lin.dtype), dwd.to(eb.dst_lin.dtype), dbd.to(eb.bias.dtype)] + eg[1:]
 
 
 class GMPFn(torch.autograd.Function):
@@ -495,17 +618,10 @@ class GMPFn(torch.autograd.Function):
         ea, ehp, est = _alloc_saves(es, E, dt, dev, train and not fused)
         na, nhp, nst = _alloc_saves(ns, N, dt, dev, train)
         P = None
+        sz = x.element_size()
         if spec.trick:
-            P = torch.empty(N, 2 * H, dtype=dt, device=dev)
-            sz = x.element_size()
-            if proj_kernel_ok(x, H):
-                proj_forward(N, x, spec.pack["proj"], spec.pack["proj_b"], P,
-                             tag="proj", cost=with_alg(alg8d_node(N, H, sz), cost_proj(N, H, sz)))
-            else:
-                mlp_forward(rows=N, dtype=dt, hidden=H, nlin=1, out_dim=2 * H,
-                            segs=[(L.SEG_PLAIN, x.shape[1], x.stride(0), x, None, None)],
-                            wpk=[spec.pack["proj"]], bias=[spec.pack["proj_b"]], out=P,
-                            tag="proj", cost=with_alg(alg8d_node(N, H, sz), cost_proj(N, H, sz)))
+            P = _proj_forward(spec, x, kernel=True, tag="proj",
+                              cost=with_alg(alg8d_node(N, H, sz), cost_proj(N, H, sz)))
             if e32:
                 edge_forward(rows=E, wpk=es.wpk(), bias=es.biases(), ln=es.lnp(), e=e, proj=P, src=level.src,
                              dst=level.dst, out=e_out, a1=a1s, stats=sts, agg=agg, rowptr=level.rowptr if eagg else None,
@@ -513,40 +629,29 @@ class GMPFn(torch.autograd.Function):
                                                            cost_edge_fwd(E, N, H, sz, es.nlin, False, a1_saves=saved,
                                                                          agg=eagg)))
             else:
-                mlp_forward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H,
-                            segs=[(L.SEG_PLAIN, H, e.stride(0), e, None, None)],
+                mlp_forward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H, segs=[_plain(e, H)],
                             wpk=es.wpk(), bias=es.biases(), ln=es.lnp(), proj=P, src=level.src, dst=level.dst,
                             resid=e, out=e_out, acts=ea, hpre=ehp, stats=est,
                             tag="edge_fwd", cost=with_alg(alg8d_edge(E, N, H, sz), cost_edge_fwd(E, N, H, sz, es.nlin,
                                                                                                 train and not fused)))
         else:
-            se = (L.SEG_PLAIN, H, e.stride(0), e, None, None)
-            ss = (L.SEG_GATHER, H, x.stride(0), x, level.src, None)
-            sd = (L.SEG_GATHER, H, x.stride(0), x, level.dst, None)
+            se, ss, sd = _plain(e, H), _gather(x, level.src, H), _gather(x, level.dst, H)
             mlp_forward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H,
                         segs=[ss, sd, se] if spec.gmp_order else [se, ss, sd],
                         wpk=es.wpk(), bias=es.biases(), ln=es.lnp(), resid=e, out=e_out,
                         acts=ea, hpre=ehp, stats=est,
-                        tag="edge_fwd", cost=with_alg(alg8d_edge(E, N, H, x.element_size()),
-                                                       cost_edge_fwd_cat(E, N, H, x.element_size(), es.nlin, train)))
-        # receiver aggregation (mgnLayer.py:144-146): the node kernel's SUM / MEAN input segment
-        # walks each receiver's CSC range in edge order (torch_scatter's fp32 order); in training it
-        # also stores the sums for the backward. With eagg the edge kernel has formed the same sums
-        # already and they come in as a plain segment. (A separate segment-sum launch measured
-        # slower, and so did round 3's sums in the resident edge kernel: DESIGN.md §9.)
-        kind = L.SEG_MEAN if spec.aggregation == "mean" else L.SEG_SUM
+                        tag="edge_fwd", cost=with_alg(alg8d_edge(E, N, H, sz), cost_edge_fwd_cat(E, N, H, sz, es.nlin, train)))
+        # receiver aggregation: the node kernel's walk over e', which in training also stores the sums
+        # for the backward. With eagg the edge kernel has formed the same sums already and they come in
+        # as a plain segment. (A separate segment-sum launch measured slower, and so did round 3's sums
+        # in the resident edge kernel: DESIGN.md §9.)
         if eagg:
-            aseg = (L.SEG_PLAIN, H, agg.stride(0), agg, None, None)
+            aseg = _plain(agg, H)
         else:
             agg = torch.empty(N, H, dtype=dt, device=dev) if train else None
-            aseg = (kind, H, e_out.stride(0), e_out, level.rowptr, agg)
-        mlp_forward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H,
-                    segs=[(L.SEG_PLAIN, H, x.stride(0), x, None, None), aseg],
-                    wpk=ns.wpk(), bias=ns.biases(), ln=ns.lnp(), resid=x, out=x_out,
-                    acts=na, hpre=nhp, stats=nst,
-                    tag="node_fwd", cost=with_alg(alg8d_node(N, H, x.element_size()),
-                                                   cost_node_fwd(E, N, H, x.element_size(),
-                                                                 ns.nlin, train, plain_agg=eagg)))
+            aseg = _walk(spec.aggregation, e_out, level.rowptr, agg, H)
+        _node_forward(ns, x, aseg, x_out, (na, nhp, nst), resid=True, tag="node_fwd",
+                      cost=with_alg(alg8d_node(N, H, sz), cost_node_fwd(E, N, H, sz, ns.nlin, train, plain_agg=eagg)))
         ctx.spec, ctx.level = spec, level
         ctx.saves = (ea, ehp, est, na, nhp, nst, agg)
         ctx.fused, ctx.proj, ctx.esaves = fused, (P if fused and not saved else None), (a1s, sts)
@@ -566,23 +671,14 @@ class GMPFn(torch.autograd.Function):
         N, E, H = x.shape[0], e.shape[0], spec.H
         gx = _c(gx) if gx is not None else torch.zeros_like(x)
         ge = _c(ge) if ge is not None else None
-        # ---- NodeBlock: d(x), d(agg)
-        gpre_n = _alloc_gpre(ns, N, dt, dev)
-        dx = torch.empty_like(x)
-        dagg = torch.empty(N, H, dtype=dt, device=dev)
-        nb_n = bwd_nblocks(N)
-        part_n = torch.empty(nb_n, 2 * H, dtype=torch.float32, device=dev) if ns.ln else None
-        nb_n = mlp_backward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H, in_dim=2 * H, wtpk=ns.wtpk(),
-                     acts=na, g=gx, gpre=gpre_n, ln_g=ns.lnp()[0] if ns.ln else None, hpre=nhp, stats=nst,
-                     din=[(H, dx, True), (H, dagg, False)], ln_partial=part_n,
-                     tag="node_bwd", cost=with_alg(alg8d_node(N, H, x.element_size(), bwd=True, proj=spec.trick),
-                                                   cost_node_bwd(N, H, x.element_size(), ns.nlin)))
-        if spec.aggregation == "mean":  # scatter_mean backward: / max(deg, 1)
-            dagg = gather_rows(N, H, None, dagg, torch.empty_like(dagg), cnt_ptr=lv.rowptr)
+        sz = x.element_size()
+        # ---- NodeBlock: d(x) with the residual, d(agg)
+        dx, dagg, (gpre_n, part_n, nb_n) = _node_backward(
+            ns, x, (na, nhp, nst), gx, resid=True, mean_ptr=lv.rowptr if spec.aggregation == "mean" else None,
+            tag="node_bwd", cost=with_alg(alg8d_node(N, H, sz, bwd=True, proj=spec.trick), cost_node_bwd(N, H, sz, ns.nlin)))
         # ---- EdgeBlock: d(e) (+ residual), pre-activation grads
         fused = ctx.fused
         de = torch.empty_like(e)
-        sz = x.element_size()
         if fused:
             # one launch: forward recompute, LayerNorm backward, chain rule, dW1..dW3 / db1..db3
             g0 = torch.empty(E, H, dtype=dt, device=dev)
@@ -592,9 +688,6 @@ class GMPFn(torch.autograd.Function):
                 g=ge, g2=dagg, de=de, g0=g0, tag="edge_bwd", a1=a1s, stats=sts,
                 cost=with_alg(alg8d_edge(E, N, H, sz, bwd=True), cost_edge_bwd_fused(E, N, H, sz, saved=a1s is not None)))
         else:
-            nb_e = bwd_nblocks(E)
-            part_e = torch.empty(nb_e, 2 * H, dtype=torch.float32, device=dev) if es.ln else None
-            gpre_e = _alloc_gpre(es, E, dt, dev, rowmajor=(0,) if spec.trick else ())
             if spec.trick:
                 din = [(H, de, True)]
             else:
@@ -602,66 +695,31 @@ class GMPFn(torch.autograd.Function):
                 dxd = torch.empty(E, H, dtype=dt, device=dev)
                 din = [(H, dxs, False), (H, dxd, False), (H, de, True)] if spec.gmp_order else \
                     [(H, de, True), (H, dxs, False), (H, dxd, False)]
-            nb_e = mlp_backward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H, in_dim=es.in_dim,
-                                wtpk=es.wtpk(), acts=ea, g=ge, g2=dagg, gidx=lv.dst, gpre=gpre_e,
-                                ln_g=es.lnp()[0] if es.ln else None, hpre=ehp, stats=est, din=din, ln_partial=part_e,
-                                tag="edge_bwd",
-                                cost=with_alg(alg8d_edge(E, N, H, sz, bwd=True),
-                                              (cost_edge_bwd if spec.trick else cost_edge_bwd_cat)(E, N, H, sz,
-                                                                                                   es.nlin)))
+            gpre_e, part_e, nb_e = _chain_backward(
+                es, E, (ea, ehp, est), ge, din, g2=dagg, gidx=lv.dst, rowmajor=(0,) if spec.trick else (), tag="edge_bwd",
+                cost=with_alg(alg8d_edge(E, N, H, sz, bwd=True),
+                              (cost_edge_bwd if spec.trick else cost_edge_bwd_cat)(E, N, H, sz, es.nlin)))
             g0 = gpre_e[0]
-        grads_edge = []
         if spec.trick:
-            # sum-trick: h0 = e W_e^T + P_s[src] + P_d[dst]: dP by sender / receiver groups
-            # (dP_d formed on the fused kernel's dW waves, round 5, measured slower once the chain
-            # waves got faster: DESIGN.md §9 round 6)
-            dPs = segment_sum(N, H, lv.rowptr_src, lv.perm_src, g0, torch.empty(N, H, dtype=dt, device=dev))
-            dPd = torch.empty(N, H, dtype=dt, device=dev)
-            # dP_d and dW_e = G0^T e walk G0's rows in the same (CSC) order: one pass forms both,
-            # bitwise the two launches it replaces ("dP_d inside the dW_e pass")
-            dwe = None
-            if fused and wgrad_dpd_ok(g0, e):
-                dwe = torch.empty(H, H, dtype=torch.float32, device=dev)
-                wgrad_segsum(g0, e, dwe, lv.rowptr, lv.dst, dPd)
-            else:
-                segment_sum(N, H, lv.rowptr, None, g0, dPd)
-            if proj_kernel_ok(dx, H):
-                s_el = dx.element_size()
-                proj_backward(N, dPs, dPd, spec.pack["projT"], dx, tag="proj_bwd",
-                              cost=with_alg(alg8d_node(N, H, s_el, bwd=True), (4 * N * H * s_el, 4.0 * N * H * H)))
-            else:
-                mlp_forward(rows=N, dtype=dt, hidden=H, nlin=1, out_dim=H,
-                            segs=[(L.SEG_PLAIN, H, H, dPs, None, None), (L.SEG_PLAIN, H, H, dPd, None, None)],
-                            wpk=[spec.pack["projT"]], bias=[None], resid=dx, out=dx)
-            eb = spec.eb
             # E-row (edge chain) and N-row (projection, node chain) weight gradients go to separate
             # agn_wgrad launches: one split count serves all descs of a launch, and mixing 6x
             # different row counts leaves most workgroups idle behind the edge descs (measured)
             wg = WGrad("wgrad_node")
+            # (dP_d formed on the fused kernel's dW waves, round 5, measured slower once the chain
+            # waves got faster: DESIGN.md §9 round 6)
+            one_pass = fused and wgrad_dpd_ok(g0, e)
+            dwe = torch.empty(H, H, dtype=torch.float32, device=dev) if one_pass else None
+            dx, dws, dwd, dbd = _proj_backward(spec, lv, x, g0, wg, dx=dx, dwe=dwe, e=e)
             if fused:
-                if dwe is None:
-                    dwe = torch.empty(H, H, dtype=torch.float32, device=dev)
-                    we = WGrad("wgrad_edge")
-                    we.add(g0, e, dwe)
-                    we.run()
-                eg = [dwe]
-                for l in range(3):
-                    eg += [dW13[l], db13[l]]
-                eg = eg[:1] + [t if t.dtype == p.dtype else t.to(p.dtype) for t, p in zip(eg[1:], es.params()[1:7])]
-                eg += list(_ln_grads(part_e, nb_e, H, es.ln[0].dtype))
+                if not one_pass:
+                    dwe, _ = _g0_grads(es, g0, e, "wgrad_edge")
+                eg = _fused_chain_grads(es, dwe, None, dW13, db13, part_e, nb_e)
             else:
                 eg = _chain_param_grads(es, gpre_e, e, ea, part_e, nb_e, tag="wgrad_edge")
-            dws = torch.empty(H, x.shape[1], dtype=torch.float32, device=dev)
-            dwd = torch.empty(H, x.shape[1], dtype=torch.float32, device=dev)
-            dbd = torch.empty(H, dtype=torch.float32, device=dev)
-            wg.add(dPs, x, dws)
-            wg.add(dPd, x, dwd, dbd)
             grads_node = _chain_param_grads(ns, gpre_n, [x, agg], na, part_n, nb_n, wg)
             wg.run()
-            if fused and eg[0].dtype != es.linears[0][0].dtype:
-                eg[0] = eg[0].to(es.linears[0][0].dtype)
-            grads_edge = [eg[0], dws.to(eb.src_lin.dtype), dwd.to(eb.dst_lin.dtype), dbd.to(eb.bias.dtype)] + eg[1:]
-            return (dx, de, None, None, None, *grads_edge, *grads_node)
+            grads_node = _to_param_dtypes(ns, grads_node)
+            grads_edge = _splice_proj(spec, eg, dws, dwd, dbd)
         else:
             # concat edge MLP: dx += scatter_add(d x_src, src) + scatter_add(d x_dst, dst) in one pass
             # (fp32, one rounding), and W_0's x_src / x_dst column blocks from gathered operands
@@ -669,7 +727,7 @@ class GMPFn(torch.autograd.Function):
             xs, xd = (x, lv.src), (x, lv.dst)
             grads_edge = _chain_param_grads(es, gpre_e, [xs, xd, e] if spec.gmp_order else [e, xs, xd],
                                             ea, part_e, nb_e, tag="wgrad_edge")
-        grads_node = _chain_param_grads(ns, gpre_n, [x, agg], na, part_n, nb_n, tag="wgrad_node")
+            grads_node = _chain_param_grads(ns, gpre_n, [x, agg], na, part_n, nb_n, tag="wgrad_node")
         return (dx, de, None, None, None, *grads_edge, *grads_node)
 
 
@@ -729,22 +787,18 @@ class MGNv2Fn(torch.autograd.Function):
                          out=e_out, a1=a1s, stats=sts, agg=agg, rowptr=level.rowptr, mean=True, tag="edge_fwd",
                          cost=with_alg(alg8d_edge(E, 0, H, sz, agg=True),
                                        cost_edge_fwd(E, 0, H, sz, es.nlin, False, a1_saves=train, agg=True)))
-            aseg = (L.SEG_PLAIN, H, agg.stride(0), agg, None, None)
+            aseg = _plain(agg, H)
         else:
             ea, ehp, est = _alloc_saves(es, E, dt, dev, train)
-            mlp_forward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H,
-                        segs=[(L.SEG_PLAIN, H, e.stride(0), e, None, None)], wpk=es.wpk(), bias=es.biases(),
-                        ln=es.lnp(), resid=e, out=e_out, acts=ea, hpre=ehp, stats=est, tag="edge_fwd",
+            mlp_forward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H, segs=[_plain(e, H)],
+                        wpk=es.wpk(), bias=es.biases(), ln=es.lnp(), resid=e, out=e_out, acts=ea, hpre=ehp, stats=est,
+                        tag="edge_fwd",
                         cost=with_alg(alg8d_edge(E, 0, H, sz), cost_edge_fwd(E, 0, H, sz, es.nlin, train)))
-            # scatter_mean (trial1.py:68): the node kernel's MEAN segment walks each receiver's CSC range
-            # in edge order and, in training, stores the means for the weight gradient
+            # scatter_mean (trial1.py:68): in training the walk stores the means for the weight gradient
             agg = torch.empty(N, H, dtype=dt, device=dev) if train else None
-            aseg = (L.SEG_MEAN, H, e_out.stride(0), e_out, level.rowptr, agg)
-        mlp_forward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H,
-                    segs=[(L.SEG_PLAIN, H, x.stride(0), x, None, None), aseg],
-                    wpk=ns.wpk(), bias=ns.biases(), ln=ns.lnp(), resid=x, out=x_out, acts=na, hpre=nhp, stats=nst,
-                    tag="node_fwd", cost=with_alg(alg8d_node(N, H, sz),
-                                                   cost_node_fwd(E, N, H, sz, ns.nlin, train, plain_agg=fast)))
+            aseg = _walk("mean", e_out, level.rowptr, agg, H)
+        _node_forward(ns, x, aseg, x_out, (na, nhp, nst), resid=True, tag="node_fwd",
+                      cost=with_alg(alg8d_node(N, H, sz), cost_node_fwd(E, N, H, sz, ns.nlin, train, plain_agg=fast)))
         ctx.spec, ctx.level, ctx.fast = spec, level, fast
         ctx.saves = (ea, ehp, est, na, nhp, nst, agg, a1s, sts)
         ctx.save_for_backward(x, e)
@@ -762,18 +816,10 @@ class MGNv2Fn(torch.autograd.Function):
         sz = x.element_size()
         gx = _c(gx) if gx is not None else torch.zeros_like(x)
         ge = _c(ge) if ge is not None else None
-        # ---- node chain: d(x) with the residual, d(agg)
-        gpre_n = _alloc_gpre(ns, N, dt, dev)
-        dx = torch.empty_like(x)
-        dagg = torch.empty(N, H, dtype=dt, device=dev)
-        nb_n = bwd_nblocks(N)
-        part_n = torch.empty(nb_n, 2 * H, dtype=torch.float32, device=dev)
-        nb_n = mlp_backward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H, in_dim=2 * H,
-                            wtpk=ns.wtpk(), acts=na, g=gx, gpre=gpre_n, ln_g=ns.lnp()[0], hpre=nhp, stats=nst,
-                            din=[(H, dx, True), (H, dagg, False)], ln_partial=part_n, tag="node_bwd",
-                            cost=with_alg(alg8d_node(N, H, sz, bwd=True), cost_node_bwd(N, H, sz, ns.nlin)))
-        # scatter_mean backward: / max(deg, 1)
-        dagg = gather_rows(N, H, None, dagg, torch.empty_like(dagg), cnt_ptr=lv.rowptr)
+        # ---- node chain: d(x) with the residual, d(agg) with scatter_mean's / max(deg, 1)
+        dx, dagg, (gpre_n, part_n, nb_n) = _node_backward(
+            ns, x, (na, nhp, nst), gx, resid=True, mean_ptr=lv.rowptr, tag="node_bwd",
+            cost=with_alg(alg8d_node(N, H, sz, bwd=True), cost_node_bwd(N, H, sz, ns.nlin)))
         # ---- edge chain: d(e) = chain gradient + the residual's (ge + dagg[dst])
         de = torch.empty_like(e)
         if ctx.fast:
@@ -782,24 +828,11 @@ class MGNv2Fn(torch.autograd.Function):
                 rows=E, wpk=es.wpk(), wtpk0=es.wtpk()[0], bias=es.biases(), ln_g=es.lnp()[0], e=None, proj=None,
                 src=None, dst=lv.dst, g=ge, g2=dagg, de=de, g0=g0, tag="edge_bwd", a1=a1s, stats=sts,
                 cost=with_alg(alg8d_edge(E, 0, H, sz, bwd=True), cost_edge_bwd_fused(E, N, H, sz, saved=True)))
-            dw0 = torch.empty(H, H, dtype=torch.float32, device=dev)
-            db0 = torch.empty(H, dtype=torch.float32, device=dev)
-            we = WGrad("wgrad_edge")
-            we.add(g0, e, dw0, db0)
-            we.run()
-            eg = [dw0, db0]
-            for l in range(3):
-                eg += [dW13[l], db13[l]]
-            eg = [t if t.dtype == p.dtype else t.to(p.dtype) for t, p in zip(eg, es.params()[:8])]
-            eg += list(_ln_grads(part_e, nb_e, H, es.ln[0].dtype))
+            eg = _fused_chain_grads(es, *_g0_grads(es, g0, e, "wgrad_edge"), dW13, db13, part_e, nb_e)
         else:
-            nb_e = bwd_nblocks(E)
-            part_e = torch.empty(nb_e, 2 * H, dtype=torch.float32, device=dev)
-            gpre_e = _alloc_gpre(es, E, dt, dev)
-            nb_e = mlp_backward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H, in_dim=H,
-                                wtpk=es.wtpk(), acts=ea, g=ge, g2=dagg, gidx=lv.dst, gpre=gpre_e, ln_g=es.lnp()[0],
-                                hpre=ehp, stats=est, din=[(H, de, True)], ln_partial=part_e, tag="edge_bwd",
-                                cost=with_alg(alg8d_edge(E, 0, H, sz, bwd=True), cost_edge_bwd(E, N, H, sz, es.nlin)))
+            gpre_e, part_e, nb_e = _chain_backward(
+                es, E, (ea, ehp, est), ge, [(H, de, True)], g2=dagg, gidx=lv.dst, tag="edge_bwd",
+                cost=with_alg(alg8d_edge(E, 0, H, sz, bwd=True), cost_edge_bwd(E, N, H, sz, es.nlin)))
             eg = _chain_param_grads(es, gpre_e, e, ea, part_e, nb_e, tag="wgrad_edge")
         grads_node = _chain_param_grads(ns, gpre_n, [x, agg], na, part_n, nb_n, tag="wgrad_node")
         return (dx, de, None, None, None, *eg, *grads_node)
@@ -845,45 +878,45 @@ class SkipFn(torch.autograd.Function):
         return None, None
 
 
+def _pool_forward(ctx, x, maps, box):
+    """scatter_mean of x's rows into groups; maps = (ptr [n_out + 1], perm, inverse [rows], n_out): group
+    g holds the rows perm[ptr[g]:ptr[g + 1]], and inverse[r] is the group of row r."""
+    x = _c(x)
+    gptr, perm, _, n_out = maps
+    out = torch.empty(n_out, x.shape[1], dtype=x.dtype, device=x.device)
+    segment_sum(n_out, x.shape[1], gptr, perm, x, out, mean=True)
+    ctx.maps, ctx.box, ctx.n = maps, box, x.shape[0]
+    return out
+
+
+def _pool_backward(ctx, g):
+    """d x[r] = g[inverse[r]] / count (+ the up path's gradient parked in the box), one gather."""
+    gptr, _, inverse, _ = ctx.maps
+    g = _c(g)
+    add = ctx.box.take() if ctx.box is not None else None
+    dx = torch.empty(ctx.n, g.shape[1], dtype=g.dtype, device=g.device)
+    gather_rows(ctx.n, g.shape[1], inverse, g, dx, cnt_ptr=gptr, add=_c(add) if add is not None else None)
+    return dx, None, None
+
+
 class PoolNodeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pool, box=None):
-        x = _c(x)
-        out = torch.empty(pool.nc, x.shape[1], dtype=x.dtype, device=x.device)
-        segment_sum(pool.nc, x.shape[1], pool.c2f_ptr, pool.c2f, x, out, mean=True)
-        ctx.pool, ctx.box = pool, box
-        ctx.n = x.shape[0]
-        return out
+        return _pool_forward(ctx, x, (pool.c2f_ptr, pool.c2f, pool.f2c, pool.nc), box)
 
     @staticmethod
     def backward(ctx, g):
-        p = ctx.pool
-        g = _c(g)
-        add = ctx.box.take() if ctx.box is not None else None
-        dx = torch.empty(ctx.n, g.shape[1], dtype=g.dtype, device=g.device)
-        gather_rows(ctx.n, g.shape[1], p.f2c, g, dx, cnt_ptr=p.c2f_ptr, add=_c(add) if add is not None else None)
-        return dx, None, None
+        return _pool_backward(ctx, g)
 
 
 class PoolEdgeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e, pool, box=None):
-        e = _c(e)
-        ec = pool.coarse.E
-        out = torch.empty(ec, e.shape[1], dtype=e.dtype, device=e.device)
-        segment_sum(ec, e.shape[1], pool.cmem_ptr, pool.cand_sorted, e, out, mean=True)
-        ctx.pool, ctx.box = pool, box
-        ctx.n = e.shape[0]
-        return out
+        return _pool_forward(ctx, e, (pool.cmem_ptr, pool.cand_sorted, pool.inv, pool.coarse.E), box)
 
     @staticmethod
     def backward(ctx, g):
-        p = ctx.pool
-        g = _c(g)
-        add = ctx.box.take() if ctx.box is not None else None
-        de = torch.empty(ctx.n, g.shape[1], dtype=g.dtype, device=g.device)
-        gather_rows(ctx.n, g.shape[1], p.inv, g, de, cnt_ptr=p.cmem_ptr, add=_c(add) if add is not None else None)
-        return de, None, None
+        return _pool_backward(ctx, g)
 
 
 class UnpoolFn(torch.autograd.Function):
@@ -922,21 +955,16 @@ class EdgeBlockFn(torch.autograd.Function):
         require_device(x, e)
         x, e = _c(x), _c(e)
         dt, dev = x.dtype, x.device
-        N, E, H = x.shape[0], e.shape[0], spec.H
+        E, H = e.shape[0], spec.H
         es = spec.edge
         out = torch.empty(E, H, dtype=dt, device=dev)
         ea, ehp, est = _alloc_saves(es, E, dt, dev, train)
         if spec.trick:
-            P = torch.empty(N, 2 * H, dtype=dt, device=dev)
-            mlp_forward(rows=N, dtype=dt, hidden=H, nlin=1, out_dim=2 * H,
-                        segs=[(L.SEG_PLAIN, x.shape[1], x.stride(0), x, None, None)],
-                        wpk=[spec.pack["proj"]], bias=[spec.pack["proj_b"]], out=P)
-            segs = [(L.SEG_PLAIN, H, e.stride(0), e, None, None)]
+            P = _proj_forward(spec, x, kernel=False)
+            segs = [_plain(e, H)]
         else:
             P = None
-            segs = [(L.SEG_PLAIN, H, e.stride(0), e, None, None),
-                    (L.SEG_GATHER, H, x.stride(0), x, level.src, None),
-                    (L.SEG_GATHER, H, x.stride(0), x, level.dst, None)]
+            segs = [_plain(e, H), _gather(x, level.src, H), _gather(x, level.dst, H)]
         mlp_forward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H, segs=segs, wpk=es.wpk(),
                     bias=es.biases(), ln=es.lnp(), proj=P, src=level.src if P is not None else None,
                     dst=level.dst if P is not None else None, out=out, acts=ea, hpre=ehp, stats=est)
@@ -948,14 +976,11 @@ class EdgeBlockFn(torch.autograd.Function):
     def backward(ctx, g):
         x, e = ctx.saved_tensors
         spec, lv = ctx.spec, ctx.level
-        ea, ehp, est = ctx.saves
+        ea = ctx.saves[0]
         es = spec.edge
         dt, dev = x.dtype, x.device
         N, E, H = x.shape[0], e.shape[0], spec.H
         g = _c(g)
-        gpre = _alloc_gpre(es, E, dt, dev, rowmajor=(0,) if spec.trick else ())
-        nb = bwd_nblocks(E)
-        part = torch.empty(nb, 2 * H, dtype=torch.float32, device=dev) if es.ln else None
         de = torch.empty_like(e)
         if spec.trick:
             din = [(H, de, False)]
@@ -963,27 +988,13 @@ class EdgeBlockFn(torch.autograd.Function):
             dxs = torch.empty(E, H, dtype=dt, device=dev)
             dxd = torch.empty(E, H, dtype=dt, device=dev)
             din = [(H, de, False), (H, dxs, False), (H, dxd, False)]
-        nb = mlp_backward(rows=E, dtype=dt, hidden=H, nlin=es.nlin, act_fn=es.act, out_dim=H, in_dim=es.in_dim, wtpk=es.wtpk(),
-                     acts=ea, g=g, gpre=gpre, ln_g=es.lnp()[0] if es.ln else None, hpre=ehp, stats=est,
-                     din=din, ln_partial=part)
+        gpre, part, nb = _chain_backward(es, E, ctx.saves, g, din, rowmajor=(0,) if spec.trick else ())
         if spec.trick:
-            g0 = gpre[0]
-            dPs = segment_sum(N, H, lv.rowptr_src, lv.perm_src, g0, torch.empty(N, H, dtype=dt, device=dev))
-            dPd = segment_sum(N, H, lv.rowptr, None, g0, torch.empty(N, H, dtype=dt, device=dev))
-            dx = torch.zeros_like(x)
-            mlp_forward(rows=N, dtype=dt, hidden=H, nlin=1, out_dim=H,
-                        segs=[(L.SEG_PLAIN, H, H, dPs, None, None), (L.SEG_PLAIN, H, H, dPd, None, None)],
-                        wpk=[spec.pack["projT"]], bias=[None], out=dx)
-            eg = _chain_param_grads(es, gpre, e, ea, part, nb, tag="wgrad_edge")
-            eb = spec.eb
             wg = WGrad("wgrad_node")
-            dws = torch.empty(H, x.shape[1], dtype=torch.float32, device=dev)
-            dwd = torch.empty(H, x.shape[1], dtype=torch.float32, device=dev)
-            dbd = torch.empty(H, dtype=torch.float32, device=dev)
-            wg.add(dPs, x, dws)
-            wg.add(dPd, x, dwd, dbd)
+            dx, dws, dwd, dbd = _proj_backward(spec, lv, x, gpre[0], wg)
+            eg = _chain_param_grads(es, gpre, e, ea, part, nb, tag="wgrad_edge")
             wg.run()
-            grads = [eg[0], dws.to(eb.src_lin.dtype), dwd.to(eb.dst_lin.dtype), dbd.to(eb.bias.dtype)] + eg[1:]
+            grads = _splice_proj(spec, eg, dws, dwd, dbd)
         else:
             dx = segment_sum2(N, H, None, (lv.rowptr_src, lv.perm_src, dxs), (lv.rowptr, None, dxd),
                               torch.empty(N, H, dtype=dt, device=dev))
@@ -1004,11 +1015,7 @@ class NodeBlockFn(torch.autograd.Function):
         out = torch.empty(N, H, dtype=dt, device=dev)
         na, nhp, nst = _alloc_saves(ns, N, dt, dev, train)
         agg = torch.empty(N, H, dtype=dt, device=dev) if train else None
-        kind = L.SEG_MEAN if spec.aggregation == "mean" else L.SEG_SUM
-        mlp_forward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H,
-                    segs=[(L.SEG_PLAIN, H, x.stride(0), x, None, None),
-                          (kind, H, e.stride(0), e, level.rowptr, agg)],
-                    wpk=ns.wpk(), bias=ns.biases(), ln=ns.lnp(), out=out, acts=na, hpre=nhp, stats=nst)
+        _node_forward(ns, x, _walk(spec.aggregation, e, level.rowptr, agg, H), out, (na, nhp, nst), resid=False)
         ctx.spec, ctx.level, ctx.saves = spec, level, (na, nhp, nst, agg)
         ctx.save_for_backward(x, e)
         return out
@@ -1019,17 +1026,8 @@ class NodeBlockFn(torch.autograd.Function):
         spec, lv = ctx.spec, ctx.level
         na, nhp, nst, agg = ctx.saves
         ns = spec.node
-        dt, dev = x.dtype, x.device
-        N, E, H = x.shape[0], e.shape[0], spec.H
-        g = _c(g)
-        gpre = _alloc_gpre(ns, N, dt, dev)
-        dx = torch.empty_like(x)
-        dagg = torch.empty(N, H, dtype=dt, device=dev)
-        nb = bwd_nblocks(N)
-        part = torch.empty(nb, 2 * H, dtype=torch.float32, device=dev) if ns.ln else None
-        nb = mlp_backward(rows=N, dtype=dt, hidden=H, nlin=ns.nlin, act_fn=ns.act, out_dim=H, in_dim=2 * H, wtpk=ns.wtpk(),
-                     acts=na, g=g, gpre=gpre, ln_g=ns.lnp()[0] if ns.ln else None, hpre=nhp, stats=nst,
-                     din=[(H, dx, False), (H, dagg, False)], ln_partial=part)
+        E, H = e.shape[0], spec.H
+        dx, dagg, (gpre, part, nb) = _node_backward(ns, x, (na, nhp, nst), _c(g), resid=False)
         de = torch.empty_like(e)
         gather_rows(E, H, lv.dst, dagg, de, cnt_ptr=lv.rowptr if spec.aggregation == "mean" else None)
         grads = _chain_param_grads(ns, gpre, [x, agg], na, part, nb, tag="wgrad_node")
@@ -1117,8 +1115,7 @@ def _wec_args(spec, x, level, mean):
 def _wec_tx(spec, x):
     tx = torch.empty(x.shape[0], spec.out, dtype=x.dtype, device=x.device)
     mlp_forward(rows=x.shape[0], dtype=x.dtype, hidden=spec.inp, nlin=1, out_dim=spec.out,
-                segs=[(L.SEG_PLAIN, spec.inp, x.stride(0), x, None, None)],
-                wpk=[spec.pack["T"]], bias=[spec.pack["Tb"]], out=tx)
+                segs=[_plain(x, spec.inp)], wpk=[spec.pack["T"]], bias=[spec.pack["Tb"]], out=tx)
     return tx
 
 
@@ -1134,8 +1131,7 @@ class WECFn(torch.autograd.Function):
         spec.pack.update(dt, dev)
         pab = torch.empty(N, 2 * hd, dtype=dt, device=dev)
         mlp_forward(rows=N, dtype=dt, hidden=spec.inp, nlin=1, out_dim=2 * hd,
-                    segs=[(L.SEG_PLAIN, spec.inp, x.stride(0), x, None, None)],
-                    wpk=[spec.pack["W1"]], bias=[spec.pack["W1b"]], out=pab)
+                    segs=[_plain(x, spec.inp)], wpk=[spec.pack["W1"]], bias=[spec.pack["W1b"]], out=pab)
         tx = _wec_tx(spec, x)
         pos32 = pos.float().contiguous()
         w = torch.empty(E, 1, dtype=dt, device=dev)
@@ -1178,9 +1174,7 @@ class WECFn(torch.autograd.Function):
         i, o = spec.inp, spec.out
         dx = torch.empty_like(x)
         mlp_forward(rows=N, dtype=dt, hidden=i, nlin=1, out_dim=i,
-                    segs=[(L.SEG_PLAIN, o, o, dtx, None, None), (L.SEG_PLAIN, hd, hd, dpa, None, None),
-                          (L.SEG_PLAIN, hd, hd, dpb, None, None)],
-                    wpk=[spec.pack["back"]], bias=[None], out=dx)
+                    segs=[_plain(dtx), _plain(dpa), _plain(dpb)], wpk=[spec.pack["back"]], bias=[None], out=dx)
         W1 = spec.mod.edge_weight_mlp[0].weight
         dW1 = torch.empty(hd, 2 * i + 1, dtype=torch.float32, device=dev)
         db1 = torch.empty(hd, dtype=torch.float32, device=dev)
@@ -1234,8 +1228,7 @@ class WECGivenFn(torch.autograd.Function):
         check(L.lib().agn_wec_backward(C.byref(a), stream()), "wec_backward")
         dx = torch.empty_like(x)
         mlp_forward(rows=N, dtype=dt, hidden=spec.inp, nlin=1, out_dim=spec.inp,
-                    segs=[(L.SEG_PLAIN, spec.out, spec.out, dtx, None, None)],
-                    wpk=[spec.pack["backT"]], bias=[None], out=dx)
+                    segs=[_plain(dtx)], wpk=[spec.pack["backT"]], bias=[None], out=dx)
         dT = torch.empty(spec.out, spec.inp, dtype=torch.float32, device=dev)
         dTb = torch.empty(spec.out, dtype=torch.float32, device=dev)
         wg = WGrad()
