@@ -1,7 +1,7 @@
 // Shared code of the persistent "32-row tile" kernels (gfx950, bf16, H = 128): edge32_fwd.hip,
 // enc32_fwd.hip, node32_fwd.hip, node32_bwd.hip and edge_bwd.hip; the tile walk also serves the
-// resident kernels of mlp.hip and proj.hip. Each wave of these kernels streams 32-row tiles in the
-// acc layout of common.hpp and must stay bitwise equal to the general kernel (mlp.hip) on the same
+// resident kernels of mlp_general_bf16.hip and proj.hip. Each wave of these kernels streams 32-row tiles in
+// the acc layout of common.hpp and must stay bitwise equal to the general kernel (mlp_general.hpp) on the same
 // operands, so the sequences that pin that equality (the MFMA order of a streamed product, the
 // LayerNorm output steps) are written once here.
 //
