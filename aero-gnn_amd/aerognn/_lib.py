@@ -30,6 +30,7 @@ class Seg(C.Structure):
 
 # AGN_ACT_* (aerognn.h): the MLP hidden activation, mlp.py:37
 ACT = {"relu": 0, "gelu": 1, "silu": 2, "tanh": 3}
+ACT_NONE = -1  # AGN_ACT_NONE: agn_act_dropout_* without an activation
 
 
 class MlpFwdArgs(C.Structure):
@@ -138,7 +139,8 @@ LAUNCHES = ("agn_pack", "agn_mlp_forward", "agn_mlp_backward", "agn_reduce_parti
             "agn_segment_max", "agn_segment_max_backward", "agn_edge_bwd_fused", "agn_encoder_bwd_fused", "agn_wgrad_reduce",
             "agn_edge_forward32", "agn_edge_agg_fixup",
             "agn_proj_forward", "agn_proj_backward", "agn_fourier_embed", "agn_fourier_embed_bwd", "agn_eval_sums",
-            "agn_aero_forces", "agn_surface_forces", "agn_face_edges", "agn_mse_loss", "agn_adam_step")
+            "agn_aero_forces", "agn_surface_forces", "agn_face_edges", "agn_mse_loss", "agn_adam_step",
+            "agn_act_dropout_fwd", "agn_act_dropout_bwd")
 
 
 class AeroGNNError(RuntimeError):
@@ -275,6 +277,9 @@ def lib():
             "agn_mse_loss": (i32, [i32, i32, i32, i32, vp, i32, vp, i32, C.c_double, vp, vp, vp, i32, vp, vp]),
             "agn_adam_chunk_elems": (i32, []),
             "agn_adam_step": (i32, [vp, i32, vp, i32, i32, vp]),
+            "agn_act_dropout_pass_elems": (C.c_int64, []),
+            "agn_act_dropout_fwd": (i32, [i32, i32, C.c_int64, vp, vp, vp, C.c_double, C.c_uint64, C.c_uint64, vp]),
+            "agn_act_dropout_bwd": (i32, [i32, i32, C.c_int64, vp, vp, vp, vp, C.c_double, vp]),
             "agn_f64_gemm": (i32, [C.POINTER(F64GemmArgs), vp]),
             "agn_f64_wgrad_scratch_bytes": (C.c_size_t, [C.POINTER(F64WgradArgs)]),
             "agn_f64_wgrad": (i32, [C.POINTER(F64WgradArgs), vp, vp]),

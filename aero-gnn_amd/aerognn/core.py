@@ -621,6 +621,38 @@ def fourier_embed_bwd(x, d, freq_start, freq_len, with_input, g, dx):
     return dx
 
 
+def philox_draw(device, n):
+    """(seed, offset) of the device's default torch generator for a mask of n elements, and the
+    generator advanced by 4 ceil(n / 4) (Philox blocks of four words), as torch's own dropout does:
+    successive calls use disjoint counter ranges and torch.manual_seed replays them. Read on the host
+    without a device synchronisation; not safe under graph capture (the offset is then a device value)."""
+    gen = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
+    seed, offset = gen.initial_seed(), gen.get_offset()
+    gen.set_offset(offset + 4 * ((int(n) + 3) // 4))
+    return seed, offset
+
+
+def keep_mask_empty(n, dev):
+    """The keep-mask buffer of n elements: bit e & 7 of byte e >> 3 (agn_act_dropout_fwd)."""
+    return torch.empty((n + 7) // 8, dtype=torch.uint8, device=dev)
+
+
+def act_dropout_fwd(y, act, p, seed, offset, out, mask):
+    """out = dropout_p(act(y)) over the contiguous y taken flat and the keep-mask bits (uint8,
+    ceil(n / 8) bytes) of Philox4x32-10 at (seed, offset): agn_act_dropout_fwd. act: an AGN_ACT_* code
+    or L.ACT_NONE; out may be y."""
+    check(L.lib().agn_act_dropout_fwd(dt_code(y.dtype), int(act), y.numel(), ptr(y), ptr(out), ptr(mask), float(p),
+                                      int(seed), int(offset), stream()), "act_dropout_fwd")
+    return out
+
+
+def act_dropout_bwd(y, act, p, dout, mask, dy):
+    """dy = act'(y) . dropout_p's backward of dout through the saved mask (y None with L.ACT_NONE)."""
+    check(L.lib().agn_act_dropout_bwd(dt_code(dout.dtype), int(act), dout.numel(), ptr(y), ptr(dout), ptr(mask),
+                                      ptr(dy), float(p), stream()), "act_dropout_bwd")
+    return dy
+
+
 def colsum_rows(p, nw, n, out):
     """out[c] = sum_r p[r][c] over nw rows, deterministic 2-level reduction (LN parameter grads)."""
     sr = min(512, max(1, nw))

@@ -22,7 +22,8 @@ import torch
 
 from . import _lib as L
 from ._lib import check, ptr
-from .core import require_device, segment_sum, gather_rows, stream
+from .core import (act_dropout_bwd, act_dropout_fwd, gather_rows, keep_mask_empty, philox_draw, require_device,
+                   segment_sum, stream)
 
 F64 = torch.float64
 
@@ -79,10 +80,12 @@ def scatter_rows_sum(d, idx, nrows):
 
 class Chain:
     """A Linear / activation chain + optional LayerNorm bound to fp64 parameters: lins = [(W, b), ...],
-    act = the AGN_ACT_* code between the Linears (mlp.py:37)."""
+    act = the AGN_ACT_* code between the Linears (mlp.py:37). p: the probability of a
+    training-mode dropout behind every hidden activation (mlp.py:44-45; 0.0: none)."""
 
-    def __init__(self, lins, ln=None, eps=1e-5, act=0):
+    def __init__(self, lins, ln=None, eps=1e-5, act=0, p=0.0):
         self.lins, self.ln, self.eps, self.act = lins, ln, eps, act
+        self.p = float(p)
 
     def params(self):
         out = []
@@ -110,27 +113,42 @@ class MLP64Fn(torch.autograd.Function):
         dev = xs[0].device
         nl = len(chain.lins)
         relu = chain.act == L.ACT["relu"]
-        acts, pres, z = [], [], None
+        acts, pres, masks, z = [], [], [], None
         for l, (w, b) in enumerate(chain.lins):
             n = w.shape[0]
             o = torch.empty(rows, n, dtype=F64, device=dev)
             hid = l < nl - 1
-            # hidden layers: the activation in the epilogue; a non-ReLU one also keeps its input
-            kw = {} if not hid else ({"relu": True} if relu else
-                                     {"act": chain.act, "pre_out": torch.empty(rows, n, dtype=F64, device=dev)})
+            dp = chain.p if hid else 0.0
+            # hidden layers: the activation in the epilogue; a non-ReLU one also keeps its input.
+            # With dropout (agn_act_dropout_fwd): after the ReLU epilogue in place, without an activation;
+            # a non-ReLU one leaves the GEMM plain and the kernel applies it from the kept input.
+            if not hid:
+                kw = {}
+            elif relu:
+                kw = {"relu": True}
+            elif dp > 0:
+                kw, pre = {}, o
+                o = torch.empty(rows, n, dtype=F64, device=dev)
+            else:
+                kw = {"act": chain.act, "pre_out": torch.empty(rows, n, dtype=F64, device=dev)}
+            go = pre if (hid and not relu and dp > 0) else o
             if l == 0:
                 segs, k0 = [], 0
                 for x, idx in zip(xs, idxs):
                     k = x.shape[1]
                     segs.append((x, idx, k, w[:, k0:k0 + k], 1))
                     k0 += k
-                gemm(rows, n, segs, o, bias=b, adds=[(_c(t), i) for t, i in zip(adds, add_idx)], **kw)
+                gemm(rows, n, segs, go, bias=b, adds=[(_c(t), i) for t, i in zip(adds, add_idx)], **kw)
             else:
-                gemm(rows, n, [(acts[-1], None, acts[-1].shape[1], w, 1)], o, bias=b, **kw)
+                gemm(rows, n, [(acts[-1], None, acts[-1].shape[1], w, 1)], go, bias=b, **kw)
+            if dp > 0:
+                seed, offset = philox_draw(dev, o.numel())
+                masks.append(keep_mask_empty(o.numel(), dev))
+                act_dropout_fwd(go, L.ACT_NONE if relu else chain.act, dp, seed, offset, o, masks[-1])
             if hid:
                 acts.append(o)
                 if not relu:
-                    pres.append(kw["pre_out"])
+                    pres.append(go if dp > 0 else kw["pre_out"])
             else:
                 z = o
         mean = rstd = None
@@ -152,7 +170,7 @@ class MLP64Fn(torch.autograd.Function):
         ctx.meta = meta
         ctx.nsrc = [x.shape[0] for x in xs]
         ctx.nadd = [t.shape[0] for t in adds]
-        ctx.save_for_backward(*xs, *acts, z, *([mean, rstd] if chain.ln is not None else []), *pres)
+        ctx.save_for_backward(*xs, *acts, z, *([mean, rstd] if chain.ln is not None else []), *pres, *masks)
         return y
 
     @staticmethod
@@ -164,7 +182,9 @@ class MLP64Fn(torch.autograd.Function):
         acts = list(saved[ns:ns + nl - 1])
         z = saved[ns + nl - 1]
         relu = chain.act == L.ACT["relu"]
-        pres = [] if relu else list(saved[len(saved) - (nl - 1):])
+        nm = nl - 1 if chain.p > 0 else 0  # one keep-mask per hidden layer, saved last
+        masks = list(saved[len(saved) - nm:]) if nm else []
+        pres = [] if relu else list(saved[len(saved) - nm - (nl - 1):len(saved) - nm])
         gy = _c(gy)
         dev = gy.device
         pgrads = []
@@ -197,8 +217,16 @@ class MLP64Fn(torch.autograd.Function):
                 d_in = torch.empty(rows, w.shape[1], dtype=F64, device=dev)
                 # the activation's backward: ReLU on the saved activation, d(pre) = (dz W) . [a_in > 0];
                 # others at the saved pre-activation, d(pre) = (dz W) . f'(pre)
+                # (dropout: a_in is the dropped activation, whose zeros the ReLU mask also takes; the kept
+                # elements' 1 / (1 - p) and a non-ReLU derivative are agn_act_dropout_bwd's, in place)
+                dp = chain.p
                 if relu:
                     gemm(rows, w.shape[1], [(dz, None, w.shape[0], w, 0)], d_in, mask=a_in)
+                    if dp > 0:
+                        act_dropout_bwd(None, L.ACT_NONE, dp, d_in, masks[l - 1], d_in)
+                elif dp > 0:
+                    gemm(rows, w.shape[1], [(dz, None, w.shape[0], w, 0)], d_in)
+                    act_dropout_bwd(pres[l - 1], chain.act, dp, d_in, masks[l - 1], d_in)
                 else:
                     gemm(rows, w.shape[1], [(dz, None, w.shape[0], w, 0)], d_in, mask=pres[l - 1],
                          mask_act=1 + chain.act)
@@ -297,15 +325,14 @@ def _ln_of(mlp_module):
 def _check_mlp(m):
     if m.activation_fn not in L.ACT:
         raise NotImplementedError(f"aerognn float64 MLP implements activation_fn in {sorted(L.ACT)}")
-    if m.training and m.dropout.p > 0:
-        raise NotImplementedError("aerognn float64 MLP: dropout > 0 in training is not implemented")
 
 
 def mlp_chain(m):
     """models/mlp.py MLP -> Chain (the reference's layer list, mlp.py:21-35)."""
     _check_mlp(m)
+    p = m.dropout.p if m.training else 0.0  # mlp.py:44-45: behind every hidden activation
     return Chain([(l.weight, l.bias) for l in m.layers], _ln_of(m), m.layer_norm.eps if m.use_layer_norm else 1e-5,
-                 act=L.ACT[m.activation_fn])
+                 act=L.ACT[m.activation_fn], p=p)
 
 
 def mlp_forward(m, x, rows=None):

@@ -1,6 +1,7 @@
 """autograd.Functions over the libaerognn kernels: one per reference block.
 
   MLPFn        models/mlp.py:40-51 (encoders, decoder, any MLP)
+  ActDropoutFn / LayeredSpec  mlp.py:44-45 dropout(act(.)) in training: the chain Linear by Linear
   FourierEmbedFn  models/fouriermgn.py:111-151, :167-170 ([x | Fourier features] of the node input)
   GMPFn        models/mgnLayer.py:177-213 (EdgeBlockSum / EdgeBlock + NodeBlock + residuals)
   MGNv2Fn      models/trial1.py:61-73 (MeshGraphNetLayer_v2: projection-free edge update, scatter_mean)
@@ -320,6 +321,66 @@ class MLPFn(torch.autograd.Function):
                   for k0, k in _kblocks(x, spec.hidden)]
         grads = _chain_param_grads(spec, gpre, x0, ctx.acts, part, nblk)
         return (dx, None, None, None, *grads)
+
+
+# --------------------------------------------------------------------------- training-mode dropout
+class ActDropoutFn(torch.autograd.Function):
+    """dropout_p(act(y)) between two Linears of a chain in training (mlp.py:44-45):
+    agn_act_dropout_fwd / _bwd. act: an AGN_ACT_* code or L.ACT_NONE. The Philox (seed, offset) come
+    from the device's default torch generator (core.philox_draw), which the call advances; p = 0
+    draws nothing and keeps everything. Saves y (not for ACT_NONE) and the one-bit keep-mask."""
+
+    @staticmethod
+    def forward(ctx, y, act, p):
+        require_device(y)
+        y = _c(y)
+        seed, offset = _core.philox_draw(y.device, y.numel()) if p > 0 else (0, 0)
+        out = torch.empty_like(y)
+        mask = _core.keep_mask_empty(y.numel(), y.device)
+        _core.act_dropout_fwd(y, act, p, seed, offset, out, mask)
+        ctx.act, ctx.p = act, p
+        ctx.save_for_backward(mask, *([] if act == L.ACT_NONE else [y]))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mask, *ys = ctx.saved_tensors
+        g = _c(g)
+        dy = torch.empty_like(g)
+        _core.act_dropout_bwd(ys[0] if ys else None, ctx.act, ctx.p, g, mask, dy)
+        return dy, None, None
+
+
+class LayeredSpec:
+    """A models/mlp.py chain in training with dropout p > 0, which the reference applies behind every
+    hidden activation (mlp.py:41-45): every Linear is its own single-Linear ChainSpec over the SAME
+    Parameters (the LayerNorm on the last) and runs through MLPFn, with ActDropoutFn between two of
+    them, so the backward is the existing Functions'. The chain without dropout (p = 0, eval) never
+    comes here."""
+
+    def __init__(self, linears, ln, p, act="relu"):
+        self.p = float(p)
+        self.act = L.ACT[act]
+        last = len(linears) - 1
+        self.subs = [self._sub(lin, ln if l == last else None, act) for l, lin in enumerate(linears)]
+
+    @staticmethod
+    def _sub(lin, ln, act):
+        H = max(32, ((lin[0].shape[0] + 31) // 32) * 32)  # a single Linear's `hidden`: its outputs rounded up to 32
+        if H not in (32, 64, 128):
+            raise NotImplementedError(f"aerognn fused MLP supports hidden_dim 32/64/128, got {H}")
+        return ChainSpec([lin], ln, H, Pack(), act=act)
+
+    def run(self, x, rows=None):
+        """The chain on x (on x[rows]: the gather is the first Linear's)."""
+        train = torch.is_grad_enabled()
+        h = x
+        for i, s in enumerate(self.subs):
+            s.pack.update(h.dtype, h.device)
+            h = MLPFn.apply(h, s, train, rows if i == 0 else None, *s.params())
+            if i < len(self.subs) - 1:
+                h = ActDropoutFn.apply(h, self.act, self.p)
+        return h
 
 
 class PermuteRowsFn(torch.autograd.Function):

@@ -37,6 +37,11 @@ torch.compile / FakeTensorMode, and autograd formulas that are themselves torch.
       -> (float64 [G, nset, 2, 3] = sum F, sum |F|; areas float64 [C]; normals float64 [C, 3]; cells [nset, C, 4])
       cell areas, cell normals, point-to-cell means and the force sums of a 3-D surface given as points and
       a face list, one pass (inference.py:310-320 + utils.py:385-448): agn_surface_forces. No autograd.
+  act_dropout(y, act, p, training=True) -> (out like y, keep-mask uint8 [ceil(n / 8)])
+      dropout_p(act(y)) as mlp.py:44-45 applies it between two Linears, act 'relu' / 'gelu' / 'silu' /
+      'tanh' / 'none'; Philox4x32-10 masks at the (seed, offset) of the device's default torch generator,
+      which the call advances (read on the host: not under graph capture): agn_act_dropout_fwd.
+      Backward: act_dropout_backward (agn_act_dropout_bwd). ops.act_dropout(...) returns out alone.
 
 The fused MLP / MeshGraphNet-layer kernels are not registered as operators: their calls carry
 packed-weight caches and a per-level CSC plan (Python objects), so they stay
@@ -291,6 +296,83 @@ def _fourier_bwd(ctx, g):
 
 
 torch.library.register_autograd("aerognn::fourier_embed", _fourier_bwd, setup_context=_fourier_ctx)
+
+
+# ------------------------------------------------------------------------------- activation + dropout
+def _act_code(act: str) -> int:
+    from . import _lib as L
+    if act == "none":
+        return L.ACT_NONE
+    if act not in L.ACT:
+        raise ValueError(f"act_dropout: act must be 'none' or one of {sorted(L.ACT)}, got {act!r}")
+    return L.ACT[act]
+
+
+def _check_p(p: float):
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+
+
+@torch.library.custom_op("aerognn::act_dropout", mutates_args=())
+def _act_dropout(y: Tensor, act: str, p: float, training: bool = True) -> tuple[Tensor, Tensor]:
+    """(dropout_p(act(y)), keep-mask): the mask is one bit per element of y taken flat (bit e & 7 of byte
+    e >> 3), Philox4x32-10 at the (seed, offset) of the device's default torch generator, which the
+    call advances by 4 ceil(n / 4). Not training, or p = 0: act(y), all kept, nothing drawn."""
+    from .core import act_dropout_fwd, keep_mask_empty, philox_draw
+    require_device(y)
+    _check_p(p)
+    y = y.contiguous()
+    p = float(p) if training else 0.0
+    seed, offset = philox_draw(y.device, y.numel()) if p > 0 else (0, 0)
+    out = torch.empty_like(y)
+    mask = keep_mask_empty(y.numel(), y.device)
+    act_dropout_fwd(y, _act_code(act), p, seed, offset, out, mask)
+    return out, mask
+
+
+@_act_dropout.register_fake
+def _(y, act, p, training=True):
+    return torch.empty_like(y, memory_format=torch.contiguous_format), y.new_empty((y.numel() + 7) // 8,
+                                                                                   dtype=torch.uint8)
+
+
+@torch.library.custom_op("aerognn::act_dropout_backward", mutates_args=())
+def act_dropout_backward(grad: Tensor, y: Tensor, mask: Tensor, act: str, p: float) -> Tensor:
+    from .core import act_dropout_bwd
+    require_device(grad, y, mask)
+    _check_p(p)
+    grad, y = grad.contiguous(), y.contiguous()
+    # the kernel trusts the sizes: a shorter y or mask would be read past its end
+    if grad.shape != y.shape or grad.dtype != y.dtype or mask.dtype != torch.uint8 \
+            or mask.numel() != (y.numel() + 7) // 8 or not mask.is_contiguous():
+        raise ValueError("act_dropout_backward: grad must have y's dtype and shape, mask ceil(n / 8) uint8 bytes")
+    return act_dropout_bwd(y, _act_code(act), p, grad, mask, torch.empty_like(grad))
+
+
+@act_dropout_backward.register_fake
+def _(grad, y, mask, act, p):
+    return torch.empty_like(grad, memory_format=torch.contiguous_format)
+
+
+def _act_dropout_ctx(ctx, inputs, output):
+    y, act, p, training = inputs
+    ctx.save_for_backward(y, output[1])
+    ctx.cfg = (act, float(p) if training else 0.0)
+
+
+def _act_dropout_bwd(ctx, g, g_mask):
+    y, mask = ctx.saved_tensors
+    return torch.ops.aerognn.act_dropout_backward(g, y, mask, *ctx.cfg), None, None, None
+
+
+torch.library.register_autograd("aerognn::act_dropout", _act_dropout_bwd, setup_context=_act_dropout_ctx)
+
+
+def act_dropout(y: Tensor, act: str, p: float, training: bool = True) -> Tensor:
+    """dropout(act(y)) as the reference's MLP applies it between two Linears (mlp.py:44-45): act 'relu' /
+    'gelu' / 'silu' / 'tanh' / 'none', training-mode dropout of probability p on torch's generator.
+    torch.ops.aerognn.act_dropout returns the keep-mask bits as well."""
+    return torch.ops.aerognn.act_dropout(y, act, p, training)[0]
 
 
 # ------------------------------------------------------------------------------- evaluation

@@ -2,14 +2,16 @@
 
 Module tree and parameter init order are the reference's (so torch.manual_seed gives the
 same initial weights); forward runs the whole Linear/ReLU/.../LayerNorm chain as ONE fused
-libaerognn kernel (aerognn.functions.MLPFn).
+libaerognn kernel (aerognn.functions.MLPFn). In training with dropout > 0 the chain runs Linear by
+Linear over the same Parameters with the activation + dropout kernel in between
+(aerognn.functions.LayeredSpec); p = 0 and eval mode stay on the one fused kernel.
 """
 import torch
 from torch import nn
 import torch.nn.functional as F
 
 from aerognn.core import Pack
-from aerognn.functions import ChainSpec, MLPFn
+from aerognn.functions import ChainSpec, LayeredSpec, MLPFn
 
 
 class MLP(nn.Module):
@@ -34,6 +36,7 @@ class MLP(nn.Module):
         self.hidden_dim = hidden_dim
         self.activation_fn = activation_fn
         self._spec = None
+        self._layered = None
 
     def spec(self):
         if self._spec is None:
@@ -46,12 +49,25 @@ class MLP(nn.Module):
             self._spec.check_hidden()
         return self._spec
 
+    def _dropout_on(self):
+        """Training-mode dropout applies (mlp.py:44-45): after every activation, so not with one Linear."""
+        return self.training and self.dropout.p > 0 and len(self.layers) > 1
+
+    def layered(self):
+        """The chain cut at its dropouts, cached like spec() (rebuilt when dropout.p changes)."""
+        p = float(self.dropout.p)
+        if self._layered is None or self._layered.p != p:
+            lins = [(m.weight, m.bias) for m in self.layers]
+            ln = (self.layer_norm.weight, self.layer_norm.bias) if self.use_layer_norm else None
+            self._layered = LayeredSpec(lins, ln, p, act=self.activation_fn)
+        return self._layered
+
     def forward(self, x):
         if x.dtype == torch.float64:  # train.py precision "double": agn_f64_* kernels (aerognn/f64.py)
             from aerognn import f64
             return f64.mlp_forward(self, x)
-        if self.training and self.dropout.p > 0:
-            raise NotImplementedError("aerognn fused MLP: dropout > 0 in training is not implemented")
+        if self._dropout_on():
+            return self.layered().run(x)
         s = self.spec()
         s.pack.update(x.dtype, x.device)
         return MLPFn.apply(x, s, torch.is_grad_enabled(), None, *s.params())
@@ -63,8 +79,8 @@ class MLP(nn.Module):
         if x.dtype == torch.float64:
             from aerognn import f64
             return f64.mlp_forward(self, x, rows)
-        if self.training and self.dropout.p > 0:
-            raise NotImplementedError("aerognn fused MLP: dropout > 0 in training is not implemented")
+        if self._dropout_on():
+            return self.layered().run(x, rows)
         s = self.spec()
         s.pack.update(x.dtype, x.device)
         return MLPFn.apply(x, s, torch.is_grad_enabled(), rows, *s.params())

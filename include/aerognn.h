@@ -725,6 +725,26 @@ int agn_adam_chunk_elems(void);
 int agn_adam_step(const agn_adam_desc* descs_device, int ntensor, const int32_t* chunk_map_device, int nchunk,
                   int dtype, void* stream);
 
+/* ---- training-mode dropout of the MLP chains (mlp.py:40-51 `x = dropout(act(layer(x)))`),
+ * csrc/dropout.hip: activation + dropout over a contiguous tensor of n elements taken
+ * flat, dtype AGN_F32 / AGN_BF16 / AGN_F16 / AGN_F64 (fp64 computes in double, the others in float).
+ *   forward   a = round_T(act(y)), act an AGN_ACT_* code or AGN_ACT_NONE (a = y);
+ *             out = kept ? round_T(a * scale) : 0, scale = (float)(1 / (1 - p)); out may be y itself
+ *             mask: bit e & 7 of byte e >> 3 is set iff element e is kept, ceil(n / 8) bytes
+ *   backward  da = kept ? round_T(dout * scale) : 0, dy = round_T(act_bwd(act, y, da)) (NONE: dy = da,
+ *             y unused and may be NULL); dy may be dout itself
+ * Mask: Philox4x32-10, key (lo32(seed), hi32(seed)); element e is word e & 3 of the block with counter
+ * (lo32(c), hi32(c), 0, 0), c = offset / 4 + (e >> 2), kept iff word >= min(2^32 - 1, round(p 2^32));
+ * p = 1 drops every element. It depends on (seed, offset, e, p) alone, and a call uses the counters
+ * offset / 4 .. offset / 4 + ceil(n / 4) - 1. No atomics: the same arguments give the same bytes.
+ * agn_act_dropout_pass_elems: the elements one pass of the (capped) grid covers. */
+#define AGN_ACT_NONE (-1)
+int64_t agn_act_dropout_pass_elems(void);
+int agn_act_dropout_fwd(int dtype, int act, int64_t n, const void* y, void* out, uint8_t* mask, double p,
+                        uint64_t seed, uint64_t offset, void* stream);
+int agn_act_dropout_bwd(int dtype, int act, int64_t n, const void* y, const void* dout, const uint8_t* mask, void* dy,
+                        double p, void* stream);
+
 /* ---- float64 mode (train.py:20-40 precision "double" / "float64"): the MLP / GMP path in fp64
  * on plain LDS-tiled FMA kernels (csrc/f64.hip); graph ops take dtype AGN_F64. */
 typedef struct {
