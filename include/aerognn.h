@@ -6,6 +6,10 @@
  * call performs; the Python mirror (aero-gnn_amd/models/) binds them with ctypes
  * (aero-gnn_amd/aerognn/_lib.py). Plain pointers and sizes only; every device pointer is
  * HBM memory owned by the caller; `stream` is a hipStream_t (NULL = default stream).
+ * The ctypes binding is derived from this file at import (aero-gnn_amd/aerognn/_header.py reads the
+ * declarations between extern "C" { and its }, and refuses what it cannot read), so a declaration
+ * here is all an entry point needs. A struct-typed parameter named *_device is a table in device
+ * memory and binds as a plain address; any other struct pointer is a host struct.
  * Return value: 0 on success, a hipError_t (>0) from the launch, or a negative AGN_E*
  * argument error (see agn_error_string).
  *
@@ -505,6 +509,16 @@ int agn_edge_forward32(const agn_edge_fwd_args* a, void* stream);
 int agn_edge_agg_fixup(const agn_edge_fwd_args* a, void* stream);
 /* testing: agn_edge_forward32 launches so far that formed the receiver sums (agg set) */
 long agn_debug_edge_agg_launches(void);
+/* testing: launches so far of the 32-row tile node forward kernel (csrc/node32_fwd.hip) */
+long agn_debug_node32_launches(void);
+/* testing: launches so far of the 32-row tile encoder forward kernel (csrc/enc32_fwd.hip) */
+long agn_debug_enc32_launches(void);
+/* testing: launches so far of the 32-row tile decoder forward kernel (csrc/enc32_fwd.hip) */
+long agn_debug_dec32_launches(void);
+/* testing: launches so far of the 32-row tile node backward kernel (csrc/node32_bwd.hip) */
+long agn_debug_node32_bwd_launches(void);
+/* testing: launches so far of the 32-row tile decoder backward kernel (csrc/node32_bwd.hip) */
+long agn_debug_dec32_bwd_launches(void);
 /* dw[m][k] = sum_s dw_partial[s][m][k] (and db) for each desc: the fixed-order second stage
  * of agn_wgrad on caller-provided slabs (m, k <= 128 per desc here) */
 int agn_wgrad_reduce(const agn_wgrad_batch* b, int nsplit, void* stream);

@@ -23,45 +23,112 @@ def test_library_exports_header_symbols():
     assert lib.agn_error_string(-4) == b"unsupported shape"
 
 
-def test_struct_layouts_match_c(tmp_path):
-    """ctypes mirrors (aerognn/_lib.py) agree with the C compiler's layout of include/aerognn.h."""
+def test_header_declares_every_exported_symbol():
+    """The converse: every agn_* function in the shared object's dynamic symbol table is declared in
+    include/aerognn.h (and so bound with its types)."""
     import os
+    import shutil
     import subprocess
+    from aerognn import _lib
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    if not os.path.exists(nm):
+        pytest.skip("neither nm nor llvm-nm is on this machine")
+    table = subprocess.check_output([nm, "-D", "--defined-only", _lib.LIB_PATH]).decode().splitlines()
+    exported = {f[2] for f in map(str.split, table) if len(f) == 3 and f[1] in "Tt" and f[2].startswith("agn_")}
+    names = set(_lib.exported_symbols())
+    assert len(exported) >= 20
+    assert exported <= names, sorted(exported - names)
+
+
+def test_struct_layouts_match_c(tmp_path):
+    """The structs the reader (aerognn/_header.py) builds from include/aerognn.h agree with the C
+    compiler's layout of it: the size of every struct, the offset and size of every field, pads included."""
+    from abi_layout import check_struct_layouts
     from aerognn import _lib as L
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    fields = {"agn_seg": (L.Seg, ["kind", "k", "ld", "ptr", "index", "store"]),
-              "agn_pack_desc": (L.PackDesc, ["src", "dst", "rows", "trans", "row_off", "dst_cols"]),
-              "agn_mlp_fwd_args": (L.MlpFwdArgs, ["seg", "wpk", "bias", "ln_g", "proj", "resid", "act", "stats", "mask"]),
-              "agn_mlp_bwd_args": (L.MlpBwdArgs, ["wtpk", "act", "g", "gidx", "gpre", "din_nseg", "din_k", "din",
-                                                 "din_resid", "ln_partial"]),
-              "agn_wgrad_desc": (L.WgradDesc, ["g", "x", "rows", "ldw", "dw_partial", "db", "nsplit", "xidx"]),
-              "agn_wgrad_batch": (L.WgradBatch, ["n", "d"]),
-              "agn_wec_args": (L.WecArgs, [f for f, _ in L.WecArgs._fields_ if not f.startswith("_")]),
-              "agn_edge_bwd_args": (L.EdgeBwdArgs, [f for f, _ in L.EdgeBwdArgs._fields_]),
-              "agn_edge_fwd_args": (L.EdgeFwdArgs, [f for f, _ in L.EdgeFwdArgs._fields_]),
-              "agn_f64_seg": (L.F64Seg, [f for f, _ in L.F64Seg._fields_]),
-              "agn_f64_gemm_args": (L.F64GemmArgs, [f for f, _ in L.F64GemmArgs._fields_ if not f.startswith("_")]),
-              "agn_f64_wgrad_args": (L.F64WgradArgs, [f for f, _ in L.F64WgradArgs._fields_
-                                                      if not f.startswith("_")])}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "aerognn.h"', 'int main(void){']
-    for st, (_, fs) in fields.items():
-        lines.append(f'printf("{st} size %zu\\n", sizeof({st}));')
-        for f in fs:
-            lines.append(f'printf("{st} {f} %zu\\n", offsetof({st}, {f}));')
-    lines.append("return 0;}")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)]).decode().split("\n")
-    for line in out:
-        if not line:
-            continue
-        st, f, v = line.split()
-        cls = fields[st][0]
-        want = int(v)
-        got = ctypes.sizeof(cls) if f == "size" else getattr(cls, f).offset
-        assert got == want, (st, f, got, want)
+    assert len(L.STRUCTS) >= 13
+    for st, cls in L.STRUCTS.items():
+        assert getattr(L, cls.__name__) is cls, st
+    seen = check_struct_layouts(L.STRUCTS, tmp_path)
+    assert seen == sum(1 + len(cls._fields_) for cls in L.STRUCTS.values())
+
+
+HEADER_OK = """
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define AGN_N 2
+enum { AGN_A = 0, AGN_B = (-1) };
+typedef struct {
+  int a, b;
+  const float* p[AGN_N];   /* two pointers */
+  int64_t n;
+} agn_t;
+int agn_f(const agn_t* t, const agn_t* table_device, int64_t n,
+          const void* const* pp, void* stream);
+DECLARATION
+const char* agn_name(void);
+#ifdef __cplusplus
+}
+#endif
+"""
+
+
+def test_header_reader_reads_its_subset():
+    from aerognn import _header as H
+    consts, structs, protos = H.parse(HEADER_OK.replace("DECLARATION", ""))
+    assert consts == {"AGN_N": 2, "AGN_A": 0, "AGN_B": -1}
+    T = structs["agn_t"]
+    assert T.__name__ == "T" and [f for f, _ in T._fields_] == ["a", "b", "p", "n"]
+    assert (T.b.offset, T.p.offset, T.p.size, T.n.offset, ctypes.sizeof(T)) == (4, 8, 16, 24, 32)
+    assert protos == {"agn_f": (ctypes.c_int, [ctypes.POINTER(T), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
+                      "agn_name": (ctypes.c_char_p, [])}
+
+
+@pytest.mark.parametrize("what,decl", [
+    ("bit-field", "typedef struct { int a : 3; int b; } agn_bits;"),
+    ("nested anonymous struct", "typedef struct { int a; struct { int b; } s; } agn_nested;"),
+    ("unnamed parameter", "int agn_g(int, void* stream);"),
+    ("unnamed pointer parameter", "int agn_g(int n, const void*);"),
+    ("function-pointer parameter", "int agn_g(void (*cb)(int), void* stream);"),
+    ("unknown type", "int agn_g(unsigned n, void* stream);"),
+    ("pointer return", "void* agn_g(int n);"),
+    ("non-integer define", "#define AGN_X 1.5"),
+    ("other directive", "#include <stdio.h>"),
+    ("named struct", "struct agn_s { int a; };"),
+])
+def test_header_reader_refuses_what_it_cannot_read(what, decl):
+    """One unsupported declaration at a time: the reader raises and names the declaration's line."""
+    from aerognn import _header as H
+    text = HEADER_OK.replace("DECLARATION", decl)
+    line = text[:text.index(decl)].count("\n") + 1
+    with pytest.raises(H.HeaderError, match=rf"^hdr\.h:{line}: "):
+        H.parse(text, "hdr.h")
+
+
+def test_header_reader_needs_the_extern_c_block():
+    from aerognn import _header as H
+    with pytest.raises(H.HeaderError):
+        H.parse("int agn_f(int n);")
+    with pytest.raises(H.HeaderError):
+        H.parse('extern "C" {\nint agn_f(int n);\n')
+
+
+def test_every_bound_function_has_the_header_arity():
+    """argtypes of every function reachable through lib() are set, with as many entries as the
+    header's prototype has parameters (counted here from the header text, not by the reader)."""
+    import re
+    from aerognn import _lib
+    lib = _lib.lib()
+    hdr = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER).read(), flags=re.S)
+    params = {m[1]: 0 if m[2].strip() == "void" else m[2].count(",") + 1
+              for m in re.finditer(r"\b(agn_\w+)\s*\(([^()]*)\)\s*;", hdr)}
+    names = _lib.exported_symbols()
+    assert sorted(params) == names and len(names) >= 96
+    for n in names:
+        f = getattr(lib._cdll, n)
+        assert f.argtypes is not None and len(f.argtypes) == params[n], n
+        assert (f.restype, list(f.argtypes)) == (_lib.PROTOS[n][0], _lib.PROTOS[n][1]), n
 
 
 @pytest.mark.parametrize("name,ctor", [

@@ -20,6 +20,8 @@ import os
 import pytest
 import torch
 
+from aerognn import _lib
+
 from golden_util import load, max_rel, params, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -258,7 +260,7 @@ def test_op_autograd_is_the_backward_op():
 
 
 # ------------------------------------------------------------------ argument errors
-E_ARG, E_DTYPE, E_SHAPE = -1, -2, -4
+E_ARG, E_DTYPE, E_SHAPE = _lib.E_ARG, _lib.E_DTYPE, _lib.E_SHAPE  # AGN_E_* of include/aerognn.h
 # (field overrides, expected code) on a valid call: n = 5, k = 6, ld = 6, d = 2, freq -3 / 7, with_input = 1
 BAD = [(dict(x=None), E_ARG), (dict(out=None), E_ARG), (dict(dtype=4), E_DTYPE), (dict(dtype=-1), E_DTYPE),
        (dict(d=0), E_SHAPE), (dict(d=7), E_SHAPE), (dict(freq_len=0), E_SHAPE), (dict(freq_len=33), E_SHAPE),

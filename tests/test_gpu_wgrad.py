@@ -16,6 +16,8 @@ import os
 import pytest
 import torch
 
+from aerognn import _lib
+
 import wgradref as R
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +28,7 @@ IDS = ["fp32", "bf16", "fp16"]
 ROWS = [1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 200, 333]
 MK = [(1, 1), (4, 128), (128, 4), (128, 6), (7, 12), (100, 100), (128, 129), (129, 128), (128, 256), (256, 128),
       (200, 260), (260, 6)]
-E_ARG, E_DTYPE, E_SHAPE = -1, -2, -4  # include/aerognn.h
+E_ARG, E_DTYPE, E_SHAPE = _lib.E_ARG, _lib.E_DTYPE, _lib.E_SHAPE  # AGN_E_* of include/aerognn.h
 
 
 # --------------------------------------------------------------------------- shared inputs (never modified)

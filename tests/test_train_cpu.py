@@ -5,8 +5,6 @@ fallback: bitwise steps, state dicts in both directions, ReduceLROnPlateau, the 
 train() / evaluate() with a generic loss_fn return the value of the reference's loop."""
 import copy
 import ctypes
-import os
-import subprocess
 import types
 
 import numpy as np
@@ -18,7 +16,7 @@ from aerognn import _lib as L
 from aerognn import optim as agn_optim
 from aerognn import train as agn_train
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_layout import check_struct_layouts
 
 
 def test_header_declares_train_entries():
@@ -36,28 +34,10 @@ def test_header_declares_train_entries():
 
 
 def test_new_struct_layouts_match_c(tmp_path):
-    """The check of test_cpu_boundary.test_struct_layouts_match_c for the structs of this block."""
-    fields = {"agn_adam_desc": (L.AdamDesc, [f for f, _ in L.AdamDesc._fields_ if not f.startswith("_")])}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "aerognn.h"', 'int main(void){']
-    for st, (_, fs) in fields.items():
-        lines.append(f'printf("{st} size %zu\\n", sizeof({st}));')
-        for f in fs:
-            lines.append(f'printf("{st} {f} %zu\\n", offsetof({st}, {f}));')
-    lines.append("return 0;}")
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    seen = 0
-    for line in subprocess.check_output([str(exe)]).decode().split("\n"):
-        if not line:
-            continue
-        st, f, v = line.split()
-        cls = fields[st][0]
-        got = ctypes.sizeof(cls) if f == "size" else getattr(cls, f).offset
-        assert got == int(v), (st, f, got, int(v))
-        seen += 1
-    assert seen == 1 + len(fields["agn_adam_desc"][1])
+    """The check of test_cpu_boundary.test_struct_layouts_match_c for the struct of this block: its size,
+    every field's offset and size, and numpy's view of it, through which aerognn.optim fills the table."""
+    seen = check_struct_layouts({"agn_adam_desc": L.AdamDesc}, tmp_path)
+    assert seen == 1 + len(L.AdamDesc._fields_) == 14
     assert np.dtype(L.AdamDesc).itemsize == ctypes.sizeof(L.AdamDesc)
 
 
