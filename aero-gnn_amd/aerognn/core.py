@@ -5,6 +5,7 @@ Everything here runs on the caller's current HIP stream; nothing synchronises.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -100,6 +101,18 @@ def is_tiled(t) -> bool:
 
 def logical_rows(t) -> int:
     return getattr(t, "agn_rows", t.shape[0])
+
+
+def switch(name, on=True):
+    """The AEROGNN_<name> on/off switch of an A/B path, read at every call (tests set it per case):
+    on unless set to "0"; an opt-in one (on=False) only when set to "1"."""
+    v = os.environ.get("AEROGNN_" + name)
+    return v != "0" if on else v == "1"
+
+
+def _c(t):
+    """t with dense rows: as it is when contiguous, else a copy."""
+    return t if t.is_contiguous() else t.contiguous()
 
 
 def require_device(*ts):
@@ -245,8 +258,7 @@ def mlp_forward(*, rows, dtype, hidden, nlin, out_dim, segs, wpk, bias, out, out
 # The persistent projection kernels (csrc/proj.hip) for the sum-trick edge block's node-row
 # GEMMs; bitwise identical to the general-kernel path, which AEROGNN_PROJ_KERNEL=0 selects.
 def proj_kernel_ok(x, H):
-    import os
-    return (os.environ.get("AEROGNN_PROJ_KERNEL", "1") != "0" and x.dtype == torch.bfloat16 and H == 128
+    return (switch("PROJ_KERNEL") and x.dtype == torch.bfloat16 and H == 128
             and x.dim() == 2 and x.shape[1] == 128 and x.stride(1) == 1)
 
 
@@ -300,7 +312,7 @@ def mlp_backward(*, rows, dtype, hidden, nlin, out_dim, in_dim, wtpk, acts, g, g
 
 # AEROGNN_CHECK_FAULTS=1 (set by the test suite): read the device fault word after every
 # persistent hand-off launch (a device synchronisation each time; never on the timed path).
-CHECK_FAULTS = __import__("os").environ.get("AEROGNN_CHECK_FAULTS", "0") == "1"
+CHECK_FAULTS = os.environ.get("AEROGNN_CHECK_FAULTS", "0") == "1"
 STAMPS = None  # diagnostics: a uint64 device tensor of 2*8*8*16 entries (a -DAGN_EB_STAMPS library)
 
 
@@ -311,8 +323,7 @@ def fused_edge_train_ok(rows, dtype, hidden, nlin, has_ln):
     (csrc/edge_bwd.hip): 414 instead of 680 GB of HBM traffic per C3 train step (DESIGN.md §9,
     rounds 3 and 6). AEROGNN_FUSED_EDGE_BWD=0 selects the split path (saved activations,
     agn_mlp_backward + agn_wgrad) for A/B tests."""
-    import os
-    return (os.environ.get("AEROGNN_FUSED_EDGE_BWD", "1") != "0" and dtype == torch.bfloat16 and hidden == 128
+    return (switch("FUSED_EDGE_BWD") and dtype == torch.bfloat16 and hidden == 128
             and nlin == 4 and has_ln and rows >= 64 * 1024)
 
 
@@ -320,8 +331,7 @@ def edge32_ok(dtype, hidden, nlin, has_ln, act=0):
     """agn_edge_forward32 (csrc/edge32_fwd.hip) applies to the bf16 H=128 sum-trick ReLU edge chain
     (W_e + 3 Linears + LN); AEROGNN_EDGE32=0 turns it off (then the resident agn_mlp_forward kernel
     runs, bitwise the same outputs)."""
-    import os
-    return (os.environ.get("AEROGNN_EDGE32", "1") != "0" and dtype == torch.bfloat16 and hidden == 128
+    return (switch("EDGE32") and dtype == torch.bfloat16 and hidden == 128
             and nlin == 4 and has_ln and act == 0)
 
 
@@ -329,8 +339,7 @@ def edge_saves_ok():
     """The training forward saves a1 and the LayerNorm statistics for the fused backward
     (agn_edge_forward32 act[0] / stats), which then starts its recompute at Lin1 (DESIGN.md §9,
     round 6). AEROGNN_EB_SAVED=0: save nothing, recompute h0 from e and the projection rows."""
-    import os
-    return os.environ.get("AEROGNN_EB_SAVED", "1") != "0"
+    return switch("EB_SAVED")
 
 
 def edge_agg_ok(N, aggregation):
@@ -338,8 +347,7 @@ def edge_agg_ok(N, aggregation):
     agn_edge_agg_fixup), and the node kernel reads them as a plain input instead of walking e' again
     ("receiver sums inside the edge forward"): sum aggregation on levels the 32-row
     node kernel covers. AEROGNN_EDGE_AGG=0 keeps the node kernel's walk (bitwise the same outputs)."""
-    import os
-    return os.environ.get("AEROGNN_EDGE_AGG", "1") != "0" and aggregation == "add" and N >= 64 * 1024
+    return switch("EDGE_AGG") and aggregation == "add" and N >= 64 * 1024
 
 
 def v2_edge32_ok(dtype, hidden, nlin, has_ln, act, E, N, train):
@@ -349,8 +357,7 @@ def v2_edge32_ok(dtype, hidden, nlin, has_ln, act, E, N, train):
     levels of >= 65,536 edges and nodes (fused_edge_train_ok's and edge_agg_ok's thresholds).
     AEROGNN_V2_EDGE32=0, or in training AEROGNN_EB_SAVED=0 / AEROGNN_FUSED_EDGE_BWD=0 (the fused
     backward of this chain has no projection rows to recompute from), select the general kernels."""
-    import os
-    return (os.environ.get("AEROGNN_V2_EDGE32", "1") != "0" and edge32_ok(dtype, hidden, nlin, has_ln, act)
+    return (switch("V2_EDGE32") and edge32_ok(dtype, hidden, nlin, has_ln, act)
             and E >= 64 * 1024 and N >= 64 * 1024
             and (not train or (fused_edge_train_ok(E, dtype, hidden, nlin, has_ln) and edge_saves_ok())))
 
@@ -491,7 +498,6 @@ def _fused_bwd(entry, rows, wpk, bias, ln_g, dev, scratch, tag, cost, **fields):
     reduction: the per-block dW / db slabs and LayerNorm partials, the scratch buffer (scratch None:
     AEROGNN_EB_SCRATCH decides), the packed weights and biases and the stamps pointer are filled here,
     `fields` are the entry point's own arguments; then the fault word is checked (or polled)."""
-    import os
     lib = L.lib()
     H = 128
     nblk = int(lib.agn_edge_bwd_blocks(int(rows)))
@@ -499,7 +505,7 @@ def _fused_bwd(entry, rows, wpk, bias, ln_g, dev, scratch, tag, cost, **fields):
     dbp = torch.empty(3 * nblk * H, dtype=torch.float32, device=dev)
     lnp = torch.empty(nblk, 2 * H, dtype=torch.float32, device=dev)
     if scratch is None:
-        scratch = os.environ.get("AEROGNN_EB_SCRATCH", "0") == "1"
+        scratch = switch("EB_SCRATCH", False)
     scr = (torch.empty(int(lib.agn_edge_bwd_scratch_bytes(nblk)), dtype=torch.uint8, device=dev)
            if scratch else None)
     a = L.EdgeBwdArgs()
@@ -543,8 +549,7 @@ def encoder_fused_ok(spec, dtype, k, rows, need_dx):
     hidden and out, ReLU, LayerNorm) on >= 65,536 rows whose input needs no gradient (the model's
     node / edge features). Then the forward saves nothing and the backward recomputes the chain on
     chip with dW1..dW3 there. AEROGNN_FUSED_ENC_BWD=0 selects the split path."""
-    import os
-    return (os.environ.get("AEROGNN_FUSED_ENC_BWD", "1") != "0" and dtype == torch.bfloat16 and not need_dx
+    return (switch("FUSED_ENC_BWD") and dtype == torch.bfloat16 and not need_dx
             and spec.hidden == 128 and spec.out_dim == 128 and spec.nlin == 4 and spec.ln is not None
             and spec.act == L.ACT["relu"] and 1 <= k <= 16 and rows >= 64 * 1024)
 
@@ -736,8 +741,7 @@ class WGrad:
 # dW_e and the receiver sums dP_d of the sum-trick edge block in one pass over G0
 # (agn_wgrad_segsum); bitwise the segment_sum + WGrad launches that AEROGNN_WG_DPD=0 selects.
 def wgrad_dpd_ok(g, x):
-    import os
-    return (os.environ.get("AEROGNN_WG_DPD", "1") != "0" and g.dtype in (torch.bfloat16, torch.float16)
+    return (switch("WG_DPD") and g.dtype in (torch.bfloat16, torch.float16)
             and g.dtype == x.dtype and g.dim() == 2 and x.dim() == 2 and g.shape[1] == 128 and x.shape[1] == 128
             and g.stride(1) == 1 and x.stride(1) == 1 and not is_tiled(g) and not is_tiled(x))
 

@@ -21,15 +21,12 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import parts
 from ._lib import check, ptr
-from .core import (act_dropout_bwd, act_dropout_fwd, gather_rows, keep_mask_empty, philox_draw, require_device,
+from .core import (_c, act_dropout_bwd, act_dropout_fwd, gather_rows, keep_mask_empty, philox_draw, require_device,
                    segment_sum, stream)
 
 F64 = torch.float64
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def gemm(rows, n, segs, out, bias=None, adds=(), mask=None, relu=False, act=None, mask_act=0, pre_out=None):
@@ -86,6 +83,11 @@ class Chain:
     def __init__(self, lins, ln=None, eps=1e-5, act=0, p=0.0):
         self.lins, self.ln, self.eps, self.act = lins, ln, eps, act
         self.p = float(p)
+
+    @classmethod
+    def of(cls, parts, p=0.0):
+        """The chain of a parts.read() record (the binding functions.ChainSpec.of makes for the packed route)."""
+        return cls(parts.lins, parts.ln, parts.eps, L.ACT[parts.act], p)
 
     def params(self):
         out = []
@@ -258,8 +260,6 @@ class MLP64Fn(torch.autograd.Function):
             else:
                 dadds.append(dz)
         dres = [gy] if has_resid else []
-        for w, b in chain.lins:
-            pass
         # parameter grads in Chain.params() order
         for (w, b), (dw, dbias) in zip(chain.lins, lin_grads):
             pgrads.append(dw)
@@ -318,10 +318,6 @@ class SegSum64Fn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- module bindings
-def _ln_of(mlp_module):
-    return (mlp_module.layer_norm.weight, mlp_module.layer_norm.bias) if mlp_module.use_layer_norm else None
-
-
 def _check_mlp(m):
     if m.activation_fn not in L.ACT:
         raise NotImplementedError(f"aerognn float64 MLP implements activation_fn in {sorted(L.ACT)}")
@@ -331,8 +327,7 @@ def mlp_chain(m):
     """models/mlp.py MLP -> Chain (the reference's layer list, mlp.py:21-35)."""
     _check_mlp(m)
     p = m.dropout.p if m.training else 0.0  # mlp.py:44-45: behind every hidden activation
-    return Chain([(l.weight, l.bias) for l in m.layers], _ln_of(m), m.layer_norm.eps if m.use_layer_norm else 1e-5,
-                 act=L.ACT[m.activation_fn], p=p)
+    return Chain.of(parts.read(m), p)
 
 
 def mlp_forward(m, x, rows=None):
@@ -343,14 +338,9 @@ def mlp_forward(m, x, rows=None):
 
 def edge_chain(eb):
     """EdgeBlockSum (mgnLayer.py:72-105): [W_e (no bias)] + the mlp's Linears + LayerNorm."""
-    seq = list(eb.mlp)
-    if any(isinstance(s, torch.nn.Module) and not isinstance(s, (torch.nn.Linear, torch.nn.ReLU, torch.nn.LayerNorm))
-           for s in seq):
+    if any(not isinstance(s, (torch.nn.Linear, torch.nn.ReLU, torch.nn.LayerNorm)) for s in eb.mlp):
         raise NotImplementedError("aerognn float64 EdgeBlockSum: Linear / ReLU / LayerNorm chains only")
-    lins = [m for m in seq if isinstance(m, torch.nn.Linear)]
-    lns = [m for m in seq if isinstance(m, torch.nn.LayerNorm)]
-    return Chain([(eb.edge_lin, None)] + [(m.weight, m.bias) for m in lins],
-                 (lns[0].weight, lns[0].bias) if lns else None, lns[0].eps if lns else 1e-5)
+    return Chain.of(parts.read(eb))
 
 
 def edge_update(eb, x, e_csc, level, resid=False):

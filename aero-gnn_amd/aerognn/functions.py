@@ -25,17 +25,14 @@ import torch
 from . import _lib as L
 from . import core as _core
 from ._lib import check, ptr
-from .core import (Pack, WGrad, alg8d_edge, alg8d_node, bwd_nblocks, colsum_rows, cost_edge_bwd, cost_edge_bwd_cat,
+from .core import (Pack, WGrad, _c, alg8d_edge, alg8d_node, bwd_nblocks, colsum_rows, cost_edge_bwd, cost_edge_bwd_cat,
                    cost_edge_bwd_fused, cost_edge_fwd, cost_edge_fwd_cat, cost_node_bwd, cost_node_fwd, cost_proj,
                    cost_wec_bwd, cost_wec_fwd, dt_code, edge32_ok, edge_agg_ok, edge_bwd_fused, edge_forward,
                    edge_saves_ok, fused_edge_train_ok, gather_rows, mlp_backward, mlp_forward, proj_backward,
                    proj_forward, proj_kernel_ok, relu_mask_empty, require_device, scatter_rows, segment_max,
                    segment_max_backward, segment_sum, segment_sum2, stream, tiled_empty, timed, wgrad_dpd_ok,
                    wgrad_segsum, with_alg)
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
+from .parts import hidden_of, read as read_parts
 
 
 def _plain(t, k=None):
@@ -87,6 +84,11 @@ class ChainSpec:
             pack.vector(prefix + "ln_g", ln[0].numel(), [(ln[0], 0)])
             pack.vector(prefix + "ln_b", ln[1].numel(), [(ln[1], 0)])
         self.pack = pack
+
+    @classmethod
+    def of(cls, parts, hidden, pack, prefix=""):
+        """The chain of a parts.read() record."""
+        return cls(parts.lins, parts.ln, hidden, pack, prefix, act=parts.act)
 
     def wpk(self):
         return [self.pack[self.p + f"W{l}"] for l in range(self.nlin)]
@@ -332,12 +334,7 @@ class ActDropoutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, act, p):
-        require_device(y)
-        y = _c(y)
-        seed, offset = _core.philox_draw(y.device, y.numel()) if p > 0 else (0, 0)
-        out = torch.empty_like(y)
-        mask = _core.keep_mask_empty(y.numel(), y.device)
-        _core.act_dropout_fwd(y, act, p, seed, offset, out, mask)
+        y, out, mask = act_dropout_forward(y, act, p)
         ctx.act, ctx.p = act, p
         ctx.save_for_backward(mask, *([] if act == L.ACT_NONE else [y]))
         return out
@@ -345,10 +342,30 @@ class ActDropoutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         mask, *ys = ctx.saved_tensors
-        g = _c(g)
-        dy = torch.empty_like(g)
-        _core.act_dropout_bwd(ys[0] if ys else None, ctx.act, ctx.p, g, mask, dy)
-        return dy, None, None
+        return act_dropout_backward(g, ys[0] if ys else None, mask, ctx.act, ctx.p), None, None
+
+
+def act_dropout_forward(y, act, p):
+    """The one forward of the activation + dropout kernel, for ActDropoutFn and torch.ops.aerognn.act_dropout:
+    (y as the kernel read it, out, keep-mask). act: an AGN_ACT_* code or L.ACT_NONE."""
+    require_device(y)
+    y = _c(y)
+    seed, offset = _core.philox_draw(y.device, y.numel()) if p > 0 else (0, 0)
+    out = torch.empty_like(y)
+    mask = _core.keep_mask_empty(y.numel(), y.device)
+    _core.act_dropout_fwd(y, act, p, seed, offset, out, mask)
+    return y, out, mask
+
+
+def act_dropout_backward(g, y, mask, act, p):
+    """Its one backward: dy for the output gradient g (y None with L.ACT_NONE, which reads no input)."""
+    require_device(g, y, mask)
+    g, y = _c(g), (None if y is None else _c(y))
+    # the kernel trusts the sizes: a shorter y or mask would be read past its end
+    if (y is not None and (g.shape != y.shape or g.dtype != y.dtype)) or mask.dtype != torch.uint8 \
+            or mask.numel() != (g.numel() + 7) // 8 or not mask.is_contiguous():
+        raise ValueError("act_dropout_backward: grad must have y's dtype and shape, mask ceil(n / 8) uint8 bytes")
+    return _core.act_dropout_bwd(y, act, p, g, mask, torch.empty_like(g))
 
 
 class LayeredSpec:
@@ -356,20 +373,18 @@ class LayeredSpec:
     hidden activation (mlp.py:41-45): every Linear is its own single-Linear ChainSpec over the SAME
     Parameters (the LayerNorm on the last) and runs through MLPFn, with ActDropoutFn between two of
     them, so the backward is the existing Functions'. The chain without dropout (p = 0, eval) never
-    comes here."""
+    comes here. parts: the chain's parts.read() record."""
 
-    def __init__(self, linears, ln, p, act="relu"):
+    def __init__(self, parts, p):
         self.p = float(p)
-        self.act = L.ACT[act]
-        last = len(linears) - 1
-        self.subs = [self._sub(lin, ln if l == last else None, act) for l, lin in enumerate(linears)]
+        self.act = L.ACT[parts.act]
+        last = len(parts.lins) - 1
+        self.subs = [self._sub(parts._replace(lins=[lin], ln=parts.ln if l == last else None))
+                     for l, lin in enumerate(parts.lins)]
 
     @staticmethod
-    def _sub(lin, ln, act):
-        H = max(32, ((lin[0].shape[0] + 31) // 32) * 32)  # a single Linear's `hidden`: its outputs rounded up to 32
-        if H not in (32, 64, 128):
-            raise NotImplementedError(f"aerognn fused MLP supports hidden_dim 32/64/128, got {H}")
-        return ChainSpec([lin], ln, H, Pack(), act=act)
+    def _sub(parts):
+        return ChainSpec.of(parts, hidden_of(parts.lins, None), Pack())
 
     def run(self, x, rows=None):
         """The chain on x (on x[rows]: the gather is the first Linear's)."""
@@ -439,25 +454,41 @@ class FourierEmbedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, d, freq_start, freq_len, with_input):
-        require_device(x)
-        if x.dim() != 2:
-            raise ValueError(f"fourier_embed: expected a 2-D [rows, features] tensor, got shape {tuple(x.shape)}")
-        x = _rows_ld(x)
-        with_input = bool(with_input)
-        out = torch.empty(x.shape[0], fourier_width(x.shape[1], d, freq_len, with_input), dtype=x.dtype,
-                          device=x.device)
-        _core.fourier_embed(x, d, freq_start, freq_len, with_input, out)
-        ctx.cfg = (int(d), int(freq_start), int(freq_len), with_input)
+        ctx.cfg = (int(d), int(freq_start), int(freq_len), bool(with_input))
+        x, out = fourier_forward(x, *ctx.cfg)
         ctx.save_for_backward(x)
         return out
 
     @staticmethod
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
-        g = _rows_ld(g)
-        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        _core.fourier_embed_bwd(x, *ctx.cfg, g, dx)
-        return dx, None, None, None, None
+        return fourier_backward(g, x, *ctx.cfg), None, None, None, None
+
+
+def _embed_rows(t, what):
+    if t.dim() != 2:
+        raise ValueError(f"{what}: expected a 2-D [rows, features] tensor, got shape {tuple(t.shape)}")
+    return _rows_ld(t)
+
+
+def fourier_forward(x, d, freq_start, freq_len, with_input):
+    """The one forward of the Fourier embedding, for FourierEmbedFn and torch.ops.aerognn.fourier_embed:
+    (x as the kernel read it, out)."""
+    require_device(x)
+    x = _embed_rows(x, "fourier_embed")
+    out = torch.empty(x.shape[0], fourier_width(x.shape[1], d, freq_len, with_input), dtype=x.dtype, device=x.device)
+    return x, _core.fourier_embed(x, d, freq_start, freq_len, with_input, out)
+
+
+def fourier_backward(g, x, d, freq_start, freq_len, with_input):
+    """Its one backward: dx for the output gradient g."""
+    require_device(g, x)
+    x, g = _embed_rows(x, "fourier_embed_backward"), _embed_rows(g, "fourier_embed_backward")
+    # the kernel trusts the row width: a narrower grad would be read past its rows
+    if g.dtype != x.dtype or g.shape != (x.shape[0], fourier_width(x.shape[1], d, freq_len, with_input)):
+        raise ValueError("fourier_embed_backward: grad must have x's dtype and the forward output's shape")
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    return _core.fourier_embed_bwd(x, d, freq_start, freq_len, with_input, g, dx)
 
 
 # --------------------------------------------------------------------------- GMP layer
@@ -475,25 +506,21 @@ class LayerSpec:
         self.aggregation = "add"
         H = None
         if node_block is not None:
-            nbm = node_block.mlp
             self.aggregation = node_block.aggregation
             if self.aggregation not in ("add", "mean"):
                 raise ValueError(f"Unsupported aggregation method: {self.aggregation}")  # mgnLayer.py:147-148
-            H = nbm.layers[0].weight.shape[0]
-            self.node = ChainSpec([(m.weight, m.bias) for m in nbm.layers],
-                                  (nbm.layer_norm.weight, nbm.layer_norm.bias) if nbm.use_layer_norm else None,
-                                  H, self.pack, "n", act=nbm.activation_fn)
+            np_ = read_parts(node_block.mlp)
+            H = np_.lins[0][0].shape[0]
+            self.node = ChainSpec.of(np_, H, self.pack, "n")
         if edge_block is not None:
             eb = edge_block
             self.trick = hasattr(eb, "edge_lin")
+            # (an EdgeBlockSum reads as (edge_lin, None) + its Sequential's Linears, ReLU: parts.read)
+            ep = read_parts(eb if self.trick else eb.mlp)
+            He = ep.lins[0][0].shape[0]
+            H = He if H is None else H
+            self.edge = ChainSpec.of(ep, H, self.pack, "e")
             if self.trick:
-                seq = list(eb.mlp)
-                lins = [m for m in seq if isinstance(m, torch.nn.Linear)]
-                lns = [m for m in seq if isinstance(m, torch.nn.LayerNorm)]
-                He = eb.edge_lin.shape[0]
-                H = He if H is None else H
-                self.edge = ChainSpec([(eb.edge_lin, None)] + [(m.weight, m.bias) for m in lins],
-                                      (lns[0].weight, lns[0].bias) if lns else None, H, self.pack, "e")
                 node_dim = eb.src_lin.shape[1]
                 self.pack.matrix("proj", 2 * H, node_dim, [(eb.src_lin, 0, 0, False), (eb.dst_lin, H, 0, False)])
                 self.pack.matrix("projT", node_dim, 2 * H, [(eb.src_lin, 0, 0, True), (eb.dst_lin, 0, H, True)])
@@ -501,13 +528,6 @@ class LayerSpec:
                 self.eb = eb
                 if He != H or eb.src_lin.shape[0] != H:
                     raise NotImplementedError("aerognn: edge and node hidden widths must match")
-            else:
-                em = eb.mlp
-                H = em.layers[0].weight.shape[0] if H is None else H
-                self.edge = ChainSpec([(m.weight, m.bias) for m in em.layers],
-                                      (em.layer_norm.weight, em.layer_norm.bias) if em.use_layer_norm else None,
-                                      H, self.pack, "e", act=em.activation_fn)
-            # (EdgeBlockSum's chain is ReLU whatever activation_fn says: mgnLayer.py:81)
         self.H = H
         self._check_widths()
 
@@ -532,20 +552,11 @@ class LayerSpec:
         self = cls.__new__(cls)
         self.pack = Pack()
         self.trick, self.gmp_order, self.aggregation = False, True, "add"
-        acts = {torch.nn.ReLU: "relu", torch.nn.SiLU: "silu", torch.nn.GELU: "gelu", torch.nn.Tanh: "tanh"}
-        ea, na = acts.get(type(gmp.edge_mlp[1])), acts.get(type(gmp.node_mlp[1]))
-        # the kernels compute the exact (erf) GELU: a tanh-approximated one on either MLP is refused
-        tanh_gelu = any(isinstance(m[1], torch.nn.GELU) and m[1].approximate != "none"
-                        for m in (gmp.edge_mlp, gmp.node_mlp))
-        if ea is None or na is None or tanh_gelu:
-            raise NotImplementedError("aerognn GMP kernels implement ReLU / SiLU / GELU / Tanh MLPs")
-        e0, e2, eln = gmp.edge_mlp[0], gmp.edge_mlp[2], gmp.edge_mlp[3]
-        n0, n2, nln = gmp.node_mlp[0], gmp.node_mlp[2], gmp.node_mlp[3]
-        self.H = H = e0.weight.shape[0]
-        self.edge = ChainSpec([(e0.weight, e0.bias), (e2.weight, e2.bias)], (eln.weight, eln.bias), H, self.pack, "e",
-                              act=ea)
-        self.node = ChainSpec([(n0.weight, n0.bias), (n2.weight, n2.bias)], (nln.weight, nln.bias), H, self.pack, "n",
-                              act=na)
+        # (an activation the kernels do not implement, a tanh-approximated GELU among them, is refused by parts.read)
+        ep, np_ = read_parts(gmp.edge_mlp), read_parts(gmp.node_mlp)
+        self.H = H = ep.lins[0][0].shape[0]
+        self.edge = ChainSpec.of(ep, H, self.pack, "e")
+        self.node = ChainSpec.of(np_, H, self.pack, "n")
         self._check_widths(edge_in=3 * H)
         return self
 

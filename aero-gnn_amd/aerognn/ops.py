@@ -56,6 +56,9 @@ from typing import Optional
 import torch
 from torch import Tensor
 
+from . import _lib as L
+from . import functions as _fn
+from .functions import _embed_rows
 from .core import gather_rows as _gather_rows
 from .core import require_device, segment_max as _segment_max
 from .core import segment_max_backward as _segment_max_backward
@@ -242,21 +245,9 @@ def _(pos, edge_index, mean=None, std=None):
 
 
 # ------------------------------------------------------------------------------- fourier_embed
-def _embed_rows(t: Tensor, what: str) -> Tensor:
-    from .functions import _rows_ld
-    if t.dim() != 2:
-        raise ValueError(f"{what}: expected a 2-D [rows, features] tensor, got shape {tuple(t.shape)}")
-    return _rows_ld(t)
-
-
 @torch.library.custom_op("aerognn::fourier_embed", mutates_args=())
 def fourier_embed(x: Tensor, d: int, freq_start: int, freq_len: int, with_input: bool = True) -> Tensor:
-    from .core import fourier_embed as _embed
-    from .functions import fourier_width
-    require_device(x)
-    x = _embed_rows(x, "fourier_embed")
-    out = torch.empty(x.shape[0], fourier_width(x.shape[1], d, freq_len, with_input), dtype=x.dtype, device=x.device)
-    return _embed(x, d, freq_start, freq_len, with_input, out)
+    return _fn.fourier_forward(x, d, freq_start, freq_len, with_input)[1]
 
 
 @fourier_embed.register_fake
@@ -267,16 +258,7 @@ def _(x, d, freq_start, freq_len, with_input=True):
 @torch.library.custom_op("aerognn::fourier_embed_backward", mutates_args=())
 def fourier_embed_backward(grad: Tensor, x: Tensor, d: int, freq_start: int, freq_len: int,
                            with_input: bool) -> Tensor:
-    from .core import fourier_embed_bwd as _embed_bwd
-    require_device(grad, x)
-    x = _embed_rows(x, "fourier_embed_backward")
-    grad = _embed_rows(grad, "fourier_embed_backward")
-    from .functions import fourier_width
-    # the kernel trusts the row width: a narrower grad would be read past its rows
-    if grad.dtype != x.dtype or grad.shape != (x.shape[0], fourier_width(x.shape[1], d, freq_len, with_input)):
-        raise ValueError("fourier_embed_backward: grad must have x's dtype and the forward output's shape")
-    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-    return _embed_bwd(x, d, freq_start, freq_len, with_input, grad, dx)
+    return _fn.fourier_backward(grad, x, d, freq_start, freq_len, with_input)
 
 
 @fourier_embed_backward.register_fake
@@ -300,7 +282,6 @@ torch.library.register_autograd("aerognn::fourier_embed", _fourier_bwd, setup_co
 
 # ------------------------------------------------------------------------------- activation + dropout
 def _act_code(act: str) -> int:
-    from . import _lib as L
     if act == "none":
         return L.ACT_NONE
     if act not in L.ACT:
@@ -318,16 +299,9 @@ def _act_dropout(y: Tensor, act: str, p: float, training: bool = True) -> tuple[
     """(dropout_p(act(y)), keep-mask): the mask is one bit per element of y taken flat (bit e & 7 of byte
     e >> 3), Philox4x32-10 at the (seed, offset) of the device's default torch generator, which the
     call advances by 4 ceil(n / 4). Not training, or p = 0: act(y), all kept, nothing drawn."""
-    from .core import act_dropout_fwd, keep_mask_empty, philox_draw
     require_device(y)
     _check_p(p)
-    y = y.contiguous()
-    p = float(p) if training else 0.0
-    seed, offset = philox_draw(y.device, y.numel()) if p > 0 else (0, 0)
-    out = torch.empty_like(y)
-    mask = keep_mask_empty(y.numel(), y.device)
-    act_dropout_fwd(y, _act_code(act), p, seed, offset, out, mask)
-    return out, mask
+    return _fn.act_dropout_forward(y, _act_code(act), float(p) if training else 0.0)[1:]
 
 
 @_act_dropout.register_fake
@@ -338,15 +312,9 @@ def _(y, act, p, training=True):
 
 @torch.library.custom_op("aerognn::act_dropout_backward", mutates_args=())
 def act_dropout_backward(grad: Tensor, y: Tensor, mask: Tensor, act: str, p: float) -> Tensor:
-    from .core import act_dropout_bwd
     require_device(grad, y, mask)
     _check_p(p)
-    grad, y = grad.contiguous(), y.contiguous()
-    # the kernel trusts the sizes: a shorter y or mask would be read past its end
-    if grad.shape != y.shape or grad.dtype != y.dtype or mask.dtype != torch.uint8 \
-            or mask.numel() != (y.numel() + 7) // 8 or not mask.is_contiguous():
-        raise ValueError("act_dropout_backward: grad must have y's dtype and shape, mask ceil(n / 8) uint8 bytes")
-    return act_dropout_bwd(y, _act_code(act), p, grad, mask, torch.empty_like(grad))
+    return _fn.act_dropout_backward(grad, y, mask, _act_code(act), p)
 
 
 @act_dropout_backward.register_fake

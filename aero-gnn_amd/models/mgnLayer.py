@@ -21,17 +21,8 @@ def _level(edge_index, n):
     return Level.from_edge_index(edge_index, n)
 
 
-class EdgeBlock(nn.Module):
-    """Edge processing block for MeshGraphNet (mgnLayer.py:10-49)."""
-
-    def __init__(self, node_dim: int, edge_dim: int, hidden_dim: int = 128, num_hidden_layers: int = 1,
-                 activation_fn: str = 'relu', use_layer_norm: bool = True):
-        super().__init__()
-        input_dim = edge_dim + 2 * node_dim
-        self.mlp = MLP(input_dim=input_dim, hidden_dim=hidden_dim, output_dim=edge_dim,
-                       num_hidden_layers=num_hidden_layers, activation_fn=activation_fn,
-                       use_layer_norm=use_layer_norm)
-        self._spec = None
+class _EdgeForward(nn.Module):
+    """The spec and the forward that EdgeBlock and EdgeBlockSum share (mgnLayer.py:32-49, 93-105)."""
 
     def spec(self):
         if self._spec is None:
@@ -48,7 +39,20 @@ class EdgeBlock(nn.Module):
         return from_csc(out, lv)
 
 
-class EdgeBlockSum(nn.Module):
+class EdgeBlock(_EdgeForward):
+    """Edge processing block for MeshGraphNet (mgnLayer.py:10-49)."""
+
+    def __init__(self, node_dim: int, edge_dim: int, hidden_dim: int = 128, num_hidden_layers: int = 1,
+                 activation_fn: str = 'relu', use_layer_norm: bool = True):
+        super().__init__()
+        input_dim = edge_dim + 2 * node_dim
+        self.mlp = MLP(input_dim=input_dim, hidden_dim=hidden_dim, output_dim=edge_dim,
+                       num_hidden_layers=num_hidden_layers, activation_fn=activation_fn,
+                       use_layer_norm=use_layer_norm)
+        self._spec = None
+
+
+class EdgeBlockSum(_EdgeForward):
     """Sum trick + pre-project nodes (mgnLayer.py:51-105):
     h0 = W_e e + (W_s x)[row] + (W_d x)[col] + b, then ReLU/Linear chain + LN."""
 
@@ -77,20 +81,6 @@ class EdgeBlockSum(nn.Module):
             layers.append(nn.LayerNorm(edge_dim))
         self.mlp = nn.Sequential(*layers)
         self._spec = None
-
-    def spec(self):
-        if self._spec is None:
-            self._spec = LayerSpec(edge_block=self)
-        return self._spec
-
-    def forward(self, edge_attr, node_attr, edge_index):
-        lv = _level(edge_index, node_attr.shape[0])
-        if node_attr.dtype == torch.float64:  # train.py precision "double" (aerognn/f64.py)
-            return from_csc(f64.edge_update(self, node_attr, to_csc(edge_attr, lv), lv), lv)
-        s = self.spec()
-        s.pack.update(node_attr.dtype, node_attr.device)
-        out = EdgeBlockFn.apply(node_attr, to_csc(edge_attr, lv), lv, s, torch.is_grad_enabled(), *s.edge_params())
-        return from_csc(out, lv)
 
 
 class NodeBlock(nn.Module):

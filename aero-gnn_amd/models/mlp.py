@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from aerognn.core import Pack
 from aerognn.functions import ChainSpec, LayeredSpec, MLPFn
+from aerognn.parts import hidden_of, read as read_parts
 
 
 class MLP(nn.Module):
@@ -40,12 +41,8 @@ class MLP(nn.Module):
 
     def spec(self):
         if self._spec is None:
-            H = self.hidden_dim if len(self.layers) > 1 else max(32, ((self.layers[0].weight.shape[0] + 31) // 32) * 32)
-            if H not in (32, 64, 128):
-                raise NotImplementedError(f"aerognn fused MLP supports hidden_dim 32/64/128, got {H}")
-            lins = [(m.weight, m.bias) for m in self.layers]
-            ln = (self.layer_norm.weight, self.layer_norm.bias) if self.use_layer_norm else None
-            self._spec = ChainSpec(lins, ln, H, Pack(), act=self.activation_fn)
+            parts = read_parts(self)
+            self._spec = ChainSpec.of(parts, hidden_of(parts.lins, self.hidden_dim), Pack())
             self._spec.check_hidden()
         return self._spec
 
@@ -57,26 +54,12 @@ class MLP(nn.Module):
         """The chain cut at its dropouts, cached like spec() (rebuilt when dropout.p changes)."""
         p = float(self.dropout.p)
         if self._layered is None or self._layered.p != p:
-            lins = [(m.weight, m.bias) for m in self.layers]
-            ln = (self.layer_norm.weight, self.layer_norm.bias) if self.use_layer_norm else None
-            self._layered = LayeredSpec(lins, ln, p, act=self.activation_fn)
+            self._layered = LayeredSpec(read_parts(self), p)
         return self._layered
 
-    def forward(self, x):
+    def forward(self, x, rows=None):
+        """rows: the chain runs on x[rows] (forward_rows)."""
         if x.dtype == torch.float64:  # train.py precision "double": agn_f64_* kernels (aerognn/f64.py)
-            from aerognn import f64
-            return f64.mlp_forward(self, x)
-        if self._dropout_on():
-            return self.layered().run(x)
-        s = self.spec()
-        s.pack.update(x.dtype, x.device)
-        return MLPFn.apply(x, s, torch.is_grad_enabled(), None, *s.params())
-
-    def forward_rows(self, x, rows):
-        """self.forward(x[rows]) with the row gather fused into the first layer's input loads (the
-        kernel reads row rows[i] for output row i; no gathered copy): the edge encoder on the
-        caller's edge features in a level's receiver-grouped order."""
-        if x.dtype == torch.float64:
             from aerognn import f64
             return f64.mlp_forward(self, x, rows)
         if self._dropout_on():
@@ -84,3 +67,9 @@ class MLP(nn.Module):
         s = self.spec()
         s.pack.update(x.dtype, x.device)
         return MLPFn.apply(x, s, torch.is_grad_enabled(), rows, *s.params())
+
+    def forward_rows(self, x, rows):
+        """self.forward(x[rows]) with the row gather fused into the first layer's input loads (the
+        kernel reads row rows[i] for output row i; no gathered copy): the edge encoder on the
+        caller's edge features in a level's receiver-grouped order."""
+        return self.forward(x, rows)

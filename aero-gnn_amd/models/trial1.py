@@ -23,6 +23,7 @@ from aerognn.core import Pack, require_device
 from aerognn.functions import (BroadcastRowsFn, ChainSpec, GlobalPoolFn, GraphGroups, MGNv2Fn, MLPFn, V2LayerSpec,
                                from_csc, to_csc)
 from aerognn.graph import Level
+from aerognn.parts import hidden_of, read as read_parts
 
 
 def build_mlp(input_dim, hidden_dim, output_dim, num_hidden_layers=2, lay_norm=True, pooling=False, dropout=0.0):
@@ -36,14 +37,6 @@ def build_mlp(input_dim, hidden_dim, output_dim, num_hidden_layers=2, lay_norm=T
 
 
 # --------------------------------------------------------------------------- a Sequential as one chain
-def _parts(seq):
-    """([(weight, bias)] of the Linears in order, (gamma, beta) of a trailing LayerNorm or None, eps)."""
-    mods = [seq] if isinstance(seq, nn.Linear) else list(seq)
-    lins = [(m.weight, m.bias) for m in mods if isinstance(m, nn.Linear)]
-    lns = [m for m in mods if isinstance(m, nn.LayerNorm)]
-    return lins, ((lns[0].weight, lns[0].bias) if lns else None), (lns[0].eps if lns else 1e-5)
-
-
 def _refuse_dropout(seq):
     if isinstance(seq, nn.Sequential) and any(isinstance(m, nn.Dropout) and m.training and m.p > 0 for m in seq):
         raise NotImplementedError("aerognn fused MLP: dropout > 0 in training is not implemented")
@@ -53,13 +46,8 @@ def _chain_spec(seq):
     """The ChainSpec of a build_mlp Sequential (or of one Linear), built once and kept on the module."""
     spec = seq.__dict__.get("_agn_spec")
     if spec is None:
-        lins, ln, _ = _parts(seq)
-        H = lins[0][0].shape[0]
-        if len(lins) == 1:
-            H = max(32, ((H + 31) // 32) * 32)
-        if H not in (32, 64, 128):
-            raise NotImplementedError(f"aerognn fused MLP supports hidden_dim 32/64/128, got {H}")
-        spec = ChainSpec(lins, ln, H, Pack())
+        parts = read_parts(seq)
+        spec = ChainSpec.of(parts, hidden_of(parts.lins, parts.lins[0][0].shape[0]), Pack())
         spec.check_hidden()
         seq.__dict__["_agn_spec"] = spec
     return spec
@@ -70,9 +58,8 @@ def _run(seq, x, rows=None):
     _refuse_dropout(seq)
     require_device(x, rows)
     if x.dtype == torch.float64:
-        lins, ln, eps = _parts(seq)
         idx = rows.to(torch.int32).contiguous() if rows is not None else None
-        return f64.run_chain(f64.Chain(lins, ln, eps), [x], [idx])
+        return f64.run_chain(f64.Chain.of(read_parts(seq)), [x], [idx])
     s = _chain_spec(seq)
     s.pack.update(x.dtype, x.device)
     return MLPFn.apply(x, s, torch.is_grad_enabled(), rows, *s.params())
@@ -126,7 +113,7 @@ class MeshGraphNetLayer_v2(nn.Module):
 
     def spec(self):
         if self._spec is None:
-            self._spec = V2LayerSpec(_parts(self.edge_mlp)[:2], _parts(self.node_mlp)[:2])
+            self._spec = V2LayerSpec(*(read_parts(m)[:2] for m in (self.edge_mlp, self.node_mlp)))
         return self._spec
 
     def forward_level(self, x, e, level):
@@ -135,11 +122,9 @@ class MeshGraphNetLayer_v2(nn.Module):
         _refuse_dropout(self.node_mlp)
         require_device(x, e)
         if x.dtype == torch.float64:
-            el, eln, eeps = _parts(self.edge_mlp)
-            nl, nln, neps = _parts(self.node_mlp)
-            e_new = f64.run_chain(f64.Chain(el, eln, eeps), [e], resid=e)
+            e_new = f64.run_chain(f64.Chain.of(read_parts(self.edge_mlp)), [e], resid=e)
             agg = f64.SegSum64Fn.apply(e_new, level.rowptr, level.dst, x.shape[0], True)
-            return f64.run_chain(f64.Chain(nl, nln, neps), [x, agg], resid=x), e_new
+            return f64.run_chain(f64.Chain.of(read_parts(self.node_mlp)), [x, agg], resid=x), e_new
         s = self.spec()
         s.pack.update(x.dtype, x.device)
         return MGNv2Fn.apply(x, e, level, s, torch.is_grad_enabled(), *s.params())

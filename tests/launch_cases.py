@@ -150,6 +150,94 @@ def b_pool(shape, H, boxed):
     return fwd, {"x": x, "e": e, "skip": skip}
 
 
+def b_mlp_dropout(nrow, k, H, out, p):
+    """models/mlp.py in training with dropout p: the chain Linear by Linear (LayeredSpec). The forward
+    seeds torch's generator itself, so the Philox offsets of its masks are fixed."""
+    from models.mlp import MLP
+    m = _module(lambda: MLP(k, H, out, 2, "relu", p, True), F32).train()
+    x = _rand((nrow, k), F32, 2, False)
+
+    def fwd():
+        torch.manual_seed(11)
+        return {"y": m(x)}
+    return fwd, _named(m)
+
+
+def b_mlp_one_linear(nrow, k, H, out):
+    """num_hidden_layers = 0 (the one-Linear quirk of mlp.py:31-32): `hidden` is the outputs rounded
+    up to 32; with and without the LayerNorm."""
+    from models.mlp import MLP
+    ms = {tag: _module(lambda: MLP(k, H, out, 0, "relu", 0.0, ln), F32) for tag, ln in (("ln", True), ("plain", False))}
+    x = _rand((nrow, k), F32, 2)
+    leaves = {"x": x}
+    for tag, m in ms.items():
+        leaves.update({f"{tag}.{n}": p for n, p in m.named_parameters()})
+    return (lambda: {f"y_{tag}": m(x) for tag, m in ms.items()}), leaves
+
+
+def b_trial1_model(shape, H, layers):
+    """One train step of a small MeshGraphNet_v2 on a batch of two graphs: every build_mlp Sequential and
+    the bare linout as chains, the global pool and its broadcast, MGNv2Fn per layer."""
+    from models.trial1 import MeshGraphNet_v2
+    N, E = shape
+    ei, _ = _graph(N, E)
+    m = _module(lambda: MeshGraphNet_v2(6, 4, H, 3, layers), F32)
+    x, ea = _rand((N, 6), F32, 2), _rand((E, 4), F32, 3)
+    batch = (torch.arange(N) >= N // 2).long().to(DEV)
+    return (lambda: {"y": m(x, ea, ei, batch)}), {"x": x, "edge_attr": ea, **_named(m)}
+
+
+FOURIER = (2, -3, 7, True)  # d, freq_start, freq_len, with_input
+
+
+def b_fourier(nrow, k, op):
+    """[x | Fourier features] through the autograd Function or through torch.ops.aerognn.fourier_embed."""
+    import aerognn.ops  # noqa: F401  (registers the operators)
+    from aerognn.functions import FourierEmbedFn
+    x = _rand((nrow, k), F32, 2)
+    f = torch.ops.aerognn.fourier_embed if op else FourierEmbedFn.apply
+    return (lambda: {"y": f(x, *FOURIER)}), {"x": x}
+
+
+def b_act_dropout(nrow, k, p, op):
+    """dropout_p(act(y)) for 'gelu' and 'none' through ActDropoutFn or through the registered operator,
+    seeded alike inside the forward."""
+    from aerognn import _lib as L
+    from aerognn import ops
+    from aerognn.functions import ActDropoutFn
+    ys = {a: _rand((nrow, k), F32, 2 + i) for i, a in enumerate(("gelu", "none"))}
+
+    def one(a):
+        if op:
+            return ops.act_dropout(ys[a], a, p)
+        return ActDropoutFn.apply(ys[a], L.ACT_NONE if a == "none" else L.ACT[a], p)
+
+    def fwd():
+        torch.manual_seed(11)
+        return {a: one(a) for a in ys}
+    return fwd, {f"y_{a}": y for a, y in ys.items()}
+
+
+def b_f64_mlp_rows(nrow, k, H, out, rows):
+    """float64 MLP.forward_rows with an input gradient: the agn_f64_* kernels are not in the trace, the
+    grouping and the segment sum of the scattered input gradient are."""
+    from models.mlp import MLP
+    m = _module(lambda: MLP(k, H, out, 2), torch.float64)
+    x = _rand((nrow, k), torch.float64, 2)
+    idx = torch.randint(0, nrow, (rows,), generator=_gen(5)).to(DEV)
+    return (lambda: {"y": m.forward_rows(x, idx)}), {"x": x, **_named(m)}
+
+
+def b_f64_gmp(shape, H):
+    """A float64 MeshGraphNetLayer with the sum trick (aerognn/f64.py gmp_layer)."""
+    from models.mgnLayer import MeshGraphNetLayer
+    N, E = shape
+    _, lv = _graph(N, E)
+    m = _module(lambda: MeshGraphNetLayer(H, H, H, 2, 2, "relu", True, "add", True), torch.float64)
+    x, e = _xe(N, E, H, torch.float64)
+    return (lambda: dict(zip(("x'", "e'"), m.forward_level(x, e, lv)))), {"x": x, "e": e, **_named(m)}
+
+
 # --------------------------------------------------------------------------- the table
 # name -> (builder, kwargs, {AEROGNN_* switch: value})
 CASES = {}
@@ -176,6 +264,15 @@ _case("mlp_encoder_k6", b_mlp, nrow=300, k=6, dt=F32, H=128, out=128)
 _case("mlp_encoder_k6_rows_dx", b_mlp, nrow=300, k=6, dt=F32, H=128, out=128, rows=500, need_dx=True)
 _case("mlp_decoder_no_ln", b_mlp, nrow=300, k=128, dt=F32, H=128, out=3, ln=False, need_dx=True)
 _case("mlp_wide_h32", b_mlp, nrow=300, k=131, dt=F32, H=32, out=32, need_dx=True)
+# the routes that bind a reference module to a chain outside the layer Functions
+_case("mlp_dropout_h32", b_mlp_dropout, nrow=300, k=6, H=32, out=32, p=0.1)
+_case("mlp_one_linear", b_mlp_one_linear, nrow=300, k=6, H=32, out=20)
+_case("trial1_model_h32", b_trial1_model, shape=SMALL, H=32, layers=2)
+for _op in (False, True):
+    _case("fourier_op" if _op else "fourier_fn", b_fourier, nrow=300, k=5, op=_op)
+    _case("act_dropout_op" if _op else "act_dropout_fn", b_act_dropout, nrow=300, k=33, p=0.1, op=_op)
+_case("f64_mlp_rows_dx", b_f64_mlp_rows, nrow=300, k=6, H=32, out=32, rows=500)
+_case("f64_gmp_sum", b_f64_gmp, shape=SMALL, H=32)
 _case("wec", b_wec, shape=SMALL, given=False)
 _case("wec_given", b_wec, shape=SMALL, given=True)
 _case("pool_boxed", b_pool, shape=SMALL, H=32, boxed=True)

@@ -131,6 +131,14 @@ def test_every_bound_function_has_the_header_arity():
         assert (f.restype, list(f.argtypes)) == (_lib.PROTOS[n][0], _lib.PROTOS[n][1]), n
 
 
+def test_every_timed_launch_is_a_declared_function():
+    """_lib.LAUNCHES (the entry points the event timer wraps) names only functions the header declares:
+    a misspelt or removed one would silently go untimed."""
+    from aerognn import _lib
+    assert len(set(_lib.LAUNCHES)) == len(_lib.LAUNCHES)
+    assert set(_lib.LAUNCHES) <= set(_lib.exported_symbols()), sorted(set(_lib.LAUNCHES) - set(_lib.exported_symbols()))
+
+
 @pytest.mark.parametrize("name,ctor", [
     ("layer_sum_h32", "layer"), ("layer_cat_h32", "layer"), ("mgn5_f32", "mgn"), ("bsms_s4", "bsms"),
     ("bsms_s2_st3", "bsms")])

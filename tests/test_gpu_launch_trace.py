@@ -9,6 +9,7 @@ import json
 import os
 
 import pytest
+import torch
 
 import launch_cases
 
@@ -24,6 +25,16 @@ def golden():
 
 def test_golden_covers_the_case_table(golden):
     assert sorted(golden) == sorted(launch_cases.CASES)
+
+
+@pytest.mark.parametrize("kernel", ["fourier", "act_dropout"])
+def test_function_and_operator_agree(kernel, monkeypatch):
+    """The autograd Function and the registered operator of one kernel: the same launches and the same bits."""
+    (tf, xf), (to, xo) = (launch_cases.run_case(f"{kernel}_{via}", monkeypatch.setenv) for via in ("fn", "op"))
+    assert tf and tf == to
+    assert sorted(xf) == sorted(xo)
+    for k in xf:
+        assert torch.equal(xf[k], xo[k]), k
 
 
 @pytest.mark.parametrize("name", list(launch_cases.CASES))
