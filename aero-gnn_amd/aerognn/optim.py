@@ -23,6 +23,19 @@ Once every parameter has its state, a step only checks that the parameters, thei
 `self.state`, their state tensors and the gradients' layout are those of the last step (object by
 object and pointer by pointer, before anything is changed) and
 gathers the gradient pointers; anything that moved sends the step through the full partition again.
+
+Master weights. `Adam(params, ..., master_weights=True)` (a per-group option; the key is in `defaults`
+and `param_groups` only when it is set) is for the reference's `precision: bf16` / `float16`
+(train.py:30-38), whose parameters are 16-bit: torch's own step on them keeps p, exp_avg and exp_avg_sq
+in 16 bits and rounds most updates away. In such a group a bf16 / fp16 HIP parameter runs on
+agn_adam_step_master: its state holds `exp_avg` and `exp_avg_sq` in fp32 and `master_param`, an fp32 copy
+of p that the step updates and rounds into p; an element of p that something else wrote restarts from
+p (include/aerognn.h). fp32 / fp64 parameters of the group run agn_adam_step as always. Nothing is
+downgraded silently: a 16-bit parameter of such a group that cannot run on the kernel and a closure raise
+RuntimeError, and the options this module does not cover raise ValueError, at construction and at step().
+load_state_dict() keeps the three tensors fp32 (torch's casts state to the parameter's dtype), upcasts
+the 16-bit moments of a plain run's checkpoint, and keeps the optimizer's own master_weights flag when the
+checkpoint's groups have none.
 """
 from __future__ import annotations
 
@@ -33,7 +46,10 @@ from torch.optim.adam import Adam as _TorchAdam
 from . import _lib as L
 
 _CODES = {torch.float32: L.F32, torch.float64: L.F64}
+_MASTER_CODES = {torch.bfloat16: L.BF16, torch.float16: L.F16}  # parameters of a master_weights group
 _DESC = np.dtype(L.AdamDesc)
+_MASTER_DESC = np.dtype(L.AdamMasterDesc)
+_MASTER_KEYS = ("exp_avg", "exp_avg_sq", "master_param")
 
 
 def chunk_elems() -> int:
@@ -88,21 +104,26 @@ class _Table:
     """The descriptor table, chunk map and staging buffers of one (device, dtype)."""
 
     def __init__(self, device, dtype):
-        self.device, self.dtype, self.code = device, dtype, _CODES[dtype]
+        self.device, self.dtype = device, dtype
+        self.master = dtype in _MASTER_CODES  # agn_adam_master_desc entries, launched by agn_adam_step_master
+        self.code = _MASTER_CODES[dtype] if self.master else _CODES[dtype]
+        self.desc = _MASTER_DESC if self.master else _DESC
         self.sig = None
         self.flip = 0
 
-    def rebuild(self, sig, pptr, mptr, vptr, numels):
+    def rebuild(self, sig, pptr, mptr, vptr, numels, wptr):
         nt = len(pptr)
         self.nt = nt
-        self.pin = [torch.zeros(nt * _DESC.itemsize, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-        self.host = [b.numpy().view(_DESC) for b in self.pin]
+        self.pin = [torch.zeros(nt * self.desc.itemsize, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self.host = [b.numpy().view(self.desc) for b in self.pin]
         self.events = [torch.cuda.Event(), torch.cuda.Event()]
         self.armed = [False, False]
         for h in self.host:
             h["p"], h["m"], h["v"] = pptr, mptr, vptr
+            if self.master:
+                h["w"] = wptr
             h["dtype"] = self.code
-        self.dev = torch.empty(nt * _DESC.itemsize, dtype=torch.uint8, device=self.device)
+        self.dev = torch.empty(nt * self.desc.itemsize, dtype=torch.uint8, device=self.device)
         cmap = build_chunk_map(numels, chunk_elems())
         self.nchunk = int(cmap.shape[0])
         self.cmap = torch.from_numpy(np.ascontiguousarray(cmap).reshape(-1)).to(self.device)
@@ -125,22 +146,99 @@ class _Table:
         self.armed[k] = True
 
 
+def _master_state(p, st):
+    """The state of a master-weight parameter as agn_adam_step_master reads it: exp_avg, exp_avg_sq and
+    master_param contiguous fp32 on p's device; 16-bit moments are upcast (exact), a missing
+    master_param is p in fp32."""
+    if st.get("master_param") is None:
+        st["master_param"] = p.detach().float()
+    for k in _MASTER_KEYS:
+        t = st[k]
+        if t.dtype != torch.float32 or t.device != p.device or not t.is_contiguous():
+            st[k] = t.detach().to(device=p.device, dtype=torch.float32).contiguous()
+
+
 class Adam(_TorchAdam):
     """torch.optim.Adam whose step() runs on agn_adam_step where it applies (module docstring).
     `replay = False` (class or instance) partitions the parameters afresh at every step (measurements)."""
 
     replay = True
 
+    def __init__(self, params, *args, master_weights=False, **kwargs):
+        super().__init__(params, *args, **kwargs)
+        if master_weights:
+            self.defaults["master_weights"] = True  # add_param_group hands the defaults to a new group
+            for g in self.param_groups:
+                g.setdefault("master_weights", True)
+        self._check_master(None)
+
+    @staticmethod
+    def _uncovered(g):
+        """The setting of group g that this module does not cover, or None."""
+        for k in ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay", "fused"):
+            if g.get(k):
+                return f"{k}={g[k]!r}"
+        if torch.is_tensor(g["lr"]):
+            return "a tensor lr"
+        if any(torch.is_tensor(b) for b in g["betas"]):
+            return "a tensor beta"
+        return None
+
     def _covered(self) -> bool:
-        for g in self.param_groups:
-            if (g.get("amsgrad") or g.get("maximize") or g.get("capturable") or g.get("differentiable")
-                    or g.get("decoupled_weight_decay") or g.get("fused")):
-                return False
-            if torch.is_tensor(g["lr"]) or any(torch.is_tensor(b) for b in g["betas"]):
-                return False
+        return all(self._uncovered(g) is None for g in self.param_groups)
+
+    def _check_master(self, closure) -> bool:
+        """True when a group sets master_weights. Such an optimizer never takes torch's step as a whole
+        (that would step the 16-bit parameters in 16 bits): what would send it there raises instead."""
+        if not any(g.get("master_weights") for g in self.param_groups):
+            return False
+        for gi, g in enumerate(self.param_groups):
+            bad = self._uncovered(g)
+            if bad:
+                raise ValueError(f"aerognn.optim.Adam: master_weights=True cannot be combined with {bad} (param group "
+                                 f"{gi}): that setting runs torch's own step, which keeps 16-bit parameters and "
+                                 "their moments in 16 bits")
+        if closure is not None:
+            raise RuntimeError("aerognn.optim.Adam: master_weights=True does not take a closure: step(closure) runs "
+                               "torch's own step, which keeps 16-bit parameters and their moments in 16 bits")
         return True
 
-    def _qualifies(self, p) -> bool:
+    def _master_reason(self, p):
+        """Why the 16-bit parameter p of a master_weights group cannot run on agn_adam_step_master, or None."""
+        if not p.is_cuda:
+            return f"it is on {p.device}, not on a HIP device"
+        if not p.is_contiguous():
+            return "it is not contiguous"
+        g = p.grad
+        if g is not None:
+            if g.is_sparse or g.layout is not torch.strided:
+                return "its gradient is sparse"
+            if g.dtype != p.dtype or g.device != p.device:
+                return f"its gradient is {g.dtype} on {g.device}"
+            if not g.is_contiguous():
+                return "its gradient is not contiguous"
+        st = self.state.get(p)
+        if st:
+            for k in ("exp_avg", "exp_avg_sq", "master_param"):
+                t = st.get(k)
+                if k == "master_param" and t is None:
+                    continue  # a plain run's checkpoint: created from p at this step
+                if not torch.is_tensor(t) or not t.is_floating_point() or t.numel() != p.numel():
+                    return f"its state has no {k} of its size"
+            if not torch.is_tensor(st.get("step")) or st["step"].is_cuda:
+                return "its state's step is not a CPU tensor"
+        return None
+
+    def _qualifies(self, p, gi=0, master=False) -> bool:
+        if master and p.dtype in _MASTER_CODES:
+            why = self._master_reason(p)
+            if why:
+                g = self.param_groups[gi]
+                i = next(i for i, q in enumerate(g["params"]) if q is p)
+                name = repr(g["param_names"][i]) if "param_names" in g else f"{i}"
+                raise RuntimeError(f"aerognn.optim.Adam(master_weights=True): parameter {name} of group {gi} "
+                                   f"({p.dtype}, shape {tuple(p.shape)}) cannot take the master-weight step: {why}")
+            return True
         if not (p.is_cuda and p.dtype in _CODES and p.is_contiguous()):
             return False
         g = p.grad
@@ -159,7 +257,7 @@ class Adam(_TorchAdam):
 
     @torch.no_grad()
     def step(self, closure=None):
-        if closure is not None or not self._covered():
+        if not self._check_master(closure) and (closure is not None or not self._covered()):
             return _base_step(self, closure)
         plan = self.__dict__.get("_agn_plan") if self.replay else None
         if plan is not None:
@@ -172,8 +270,9 @@ class Adam(_TorchAdam):
             self._agn_plan = None
         ours, rest = [], False
         for gi, g in enumerate(self.param_groups):
+            master = bool(g.get("master_weights"))
             for p in g["params"]:
-                if self._qualifies(p):
+                if self._qualifies(p, gi, master):
                     ours.append((p, gi))
                 else:
                     rest = True
@@ -196,8 +295,9 @@ class Adam(_TorchAdam):
         are those of the last step (checked one by one, before anything is changed), so only the
         gradients are gathered.
         None: something moved, and step() partitions the parameters afresh."""
-        state_obj, count, tables = plan
-        if state_obj is not self.state or count != sum(len(g["params"]) for g in self.param_groups):
+        state_obj, count, flags, tables = plan
+        if (state_obj is not self.state or count != sum(len(g["params"]) for g in self.param_groups)
+                or flags != [bool(g.get("master_weights")) for g in self.param_groups]):
             return None
         strided = torch.strided
         state_get = self.state.get
@@ -205,7 +305,7 @@ class Adam(_TorchAdam):
         for tab, recs in tables:
             dt, device = tab.dtype, tab.device
             grads = [r[0].grad for r in recs]
-            for (p, _, st, pptr, mptr, vptr, _), g in zip(recs, grads):
+            for (p, _, st, pptr, mptr, vptr, _, wptr), g in zip(recs, grads):
                 if p.data_ptr() != pptr or p.dtype is not dt or state_get(p) is not st:
                     return None
                 if g is None:
@@ -214,6 +314,10 @@ class Adam(_TorchAdam):
                         or not g.is_contiguous() or st["exp_avg"].data_ptr() != mptr
                         or st["exp_avg_sq"].data_ptr() != vptr or st["step"].is_cuda):
                     return None
+                if wptr:
+                    w = st.get("master_param")
+                    if w is None or w.data_ptr() != wptr:
+                        return None
             work.append((tab, recs, grads))
         return work
 
@@ -233,26 +337,33 @@ class Adam(_TorchAdam):
             planned.append((tab, recs))
         # replayed only when every parameter runs here and has its state (none without a gradient so far)
         if keep_plan and all(r[2] is not None for _, recs in planned for r in recs):
-            self._agn_plan = (self.state, sum(len(g["params"]) for g in self.param_groups), planned)
+            self._agn_plan = (self.state, sum(len(g["params"]) for g in self.param_groups),
+                              [bool(g.get("master_weights")) for g in self.param_groups], planned)
 
     def _records(self, tab, items):
-        """(p, group index, state dict, p / exp_avg / exp_avg_sq pointers, numel) per tensor, creating the
-        state of a parameter that has its first gradient as torch.optim.Adam._init_group does; the
-        table is rebuilt when the list differs from the one it was built for."""
+        """(p, group index, state dict, p / exp_avg / exp_avg_sq pointers, numel, master_param pointer or
+        0) per tensor, creating the state of a parameter that has its first gradient as
+        torch.optim.Adam._init_group does (a master table: fp32 moments and master_param = p in fp32; state
+        that a plain run left is upcast, which is exact); the table is rebuilt when the list differs from
+        the one it was built for."""
         state = self.state
         recs = []
         for p, gi in items:
             st = state.get(p)  # no entry is created for a parameter without a gradient (torch creates none)
             if p.grad is not None and not st:
                 st = state[p]
+                dt = torch.float32 if tab.master else p.dtype
                 st["step"] = torch.tensor(0.0, dtype=_step_dtype())
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg"] = torch.zeros_like(p, dtype=dt, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, dtype=dt, memory_format=torch.preserve_format)
+            if st and tab.master:
+                _master_state(p, st)
             recs.append((p, gi, st if st else None, p.data_ptr(), st["exp_avg"].data_ptr() if st else 0,
-                         st["exp_avg_sq"].data_ptr() if st else 0, p.numel()))
+                         st["exp_avg_sq"].data_ptr() if st else 0, p.numel(),
+                         st["master_param"].data_ptr() if st and tab.master else 0))
         sig = tuple(r[3:] for r in recs)
         if sig != tab.sig:
-            tab.rebuild(sig, [r[3] for r in recs], [r[4] for r in recs], [r[5] for r in recs], [r[6] for r in recs])
+            tab.rebuild(sig, *([r[k] for r in recs] for k in (3, 4, 5, 6, 7)))
         return recs
 
     def _launch(self, tab, recs, grads):
@@ -286,10 +397,42 @@ class Adam(_TorchAdam):
         h["g"][li] = [grads[i].data_ptr() for i in live]
         tab.commit()
         from .core import stream
-        L.check(L.lib().agn_adam_step(tab.dev.data_ptr(), tab.nt, tab.cmap.data_ptr(), tab.nchunk, tab.code, stream()),
-                "adam_step")
+        fn = L.lib().agn_adam_step_master if tab.master else L.lib().agn_adam_step
+        L.check(fn(tab.dev.data_ptr(), tab.nt, tab.cmap.data_ptr(), tab.nchunk, tab.code, stream()),
+                "adam_step_master" if tab.master else "adam_step")
         _bump_versions([recs[i][0] for i in live])
 
     def add_param_group(self, param_group):
         self.__dict__["_agn_plan"] = None
         return super().add_param_group(param_group)
+
+    def load_state_dict(self, state_dict):
+        """torch's load_state_dict, then the fp32 state of master-weight parameters put back from
+        `state_dict` itself: torch casts every floating state tensor but `step` to the parameter's dtype
+        (through a call bound to Optimizer, which a subclass cannot replace). A group that had
+        master_weights keeps it when the checkpoint's group has no such key (a plain run's)."""
+        had = [g.get("master_weights") for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for g, flag, saved in zip(self.param_groups, had, state_dict["param_groups"]):
+            if flag is not None:
+                g.setdefault("master_weights", flag)
+            if not g.get("master_weights"):
+                continue
+            for p, pid in zip(g["params"], saved["params"]):
+                src, st = state_dict["state"].get(pid), self.state.get(p)
+                if not src or not st or p.dtype not in _MASTER_CODES:
+                    continue
+                for k in _MASTER_KEYS:
+                    t = src.get(k)
+                    if torch.is_tensor(t) and t.is_floating_point():
+                        st[k] = t.detach().to(device=p.device, dtype=torch.float32)
+
+    def master_parameters(self):
+        """(param, master_param) of every parameter that has fp32 master weights so far: the weights to
+        export from a 16-bit run."""
+        for g in self.param_groups:
+            if g.get("master_weights"):
+                for p in g["params"]:
+                    w = self.state.get(p, {}).get("master_param")
+                    if w is not None:
+                        yield p, w

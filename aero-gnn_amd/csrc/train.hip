@@ -18,6 +18,12 @@
 // walks the map with a grid stride. 16-B loads and stores where the tensor's four pointers allow it,
 // scalar otherwise. Every elementwise step is one correctly rounded operation in the tensor dtype, in
 // torch's order (the whole file is compiled with `#pragma clang fp contract(off)`: nothing is fused).
+//
+// agn_adam_step_master: the same step for bf16 / fp16 parameters (train.py:30-38 makes them 16-bit,
+// train.py:207-212 steps them) with an fp32 master copy w and fp32 moments per tensor. Per element
+// w = (bits(round_T(w)) == bits(p)) ? w : (float)p, then adam_elem<float> on (w, (float)g, m, v) exactly
+// as agn_adam_step runs it on an fp32 tensor, then p = round_T(w). 8 elements per thread where the
+// five pointers are 16-B aligned (one 16-B access for p and g, two for w, m, v), scalar otherwise.
 #include "common.hpp"
 #include "host.hpp"
 #include "aerognn.h"
@@ -123,6 +129,23 @@ AGN_DEV void adam_elem(T& p, T g, T& m, T& v, const AdamK<T>& k) {
   p = p - k.step_size * quot_rn<T>(m, denom);
 }
 
+// D: agn_adam_desc or agn_adam_master_desc (the same six doubles)
+template <typename T, typename D>
+AGN_DEV AdamK<T> adam_scalars(const D& d) {
+  AdamK<T> k;
+  k.omb1 = (T)(1.0 - d.beta1);
+  k.beta1 = (T)1 - k.omb1;
+  k.lerp_lo = fabs((double)k.omb1) < 0.5;  // torch's lerp tests the weight as rounded to the tensor dtype
+  k.beta2 = (T)d.beta2;
+  k.omb2 = (T)(1.0 - d.beta2);
+  k.eps = (T)d.eps;
+  k.wd = (T)d.weight_decay;
+  k.decay = d.weight_decay != 0.0;
+  k.step_size = (T)d.step_size;
+  k.bc2_sqrt = (T)d.bc2_sqrt;
+  return k;
+}
+
 template <typename T> struct Vec16;
 template <> struct Vec16<float> { typedef f32x4 type; static constexpr int W = 4; };
 typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -143,17 +166,7 @@ adam_kernel(const agn_adam_desc* __restrict__ descs, int ntensor, const int32_t*
     const int64_t e0 = (int64_t)ci * ADAM_CHUNK;
     if (e0 >= d.n) continue;                              // n == 0: a parameter without a gradient
     const int len = (int)min((int64_t)ADAM_CHUNK, d.n - e0);
-    AdamK<T> k;
-    k.omb1 = (T)(1.0 - d.beta1);
-    k.beta1 = (T)1 - k.omb1;
-    k.lerp_lo = fabs((double)k.omb1) < 0.5;  // torch's lerp tests the weight as rounded to the tensor dtype
-    k.beta2 = (T)d.beta2;
-    k.omb2 = (T)(1.0 - d.beta2);
-    k.eps = (T)d.eps;
-    k.wd = (T)d.weight_decay;
-    k.decay = d.weight_decay != 0.0;
-    k.step_size = (T)d.step_size;
-    k.bc2_sqrt = (T)d.bc2_sqrt;
+    const AdamK<T> k = adam_scalars<T>(d);
     T* p = (T*)d.p + e0;
     const T* g = (const T*)d.g + e0;
     T* m = (T*)d.m + e0;
@@ -176,6 +189,72 @@ adam_kernel(const agn_adam_desc* __restrict__ descs, int ntensor, const int32_t*
       reinterpret_cast<V*>(v)[i] = vv;
     }
     for (int i = nv * W + t; i < len; i += TR_THREADS) adam_elem<T>(p[i], g[i], m[i], v[i], k);
+  }
+}
+
+// ---------------------------------------------------------------------------- Adam with fp32 master weights
+typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
+constexpr int MW = 8;  // elements per thread on the wide path: 16 B of p and of g, 2 x 16 B of w, m and v
+
+// one element: pb / gb are the 16-bit patterns of p and g (T = bf16 or f16). The master follows the
+// parameter: an element whose p is not round_T(w) (something wrote p since the last step) restarts from
+// (float)p and keeps its moments; the patterns are compared, so +-0 and NaN need no case of their own.
+template <typename T>
+AGN_DEV void adam_master_elem(uint16_t& pb, uint16_t gb, float& w, float& m, float& v, const AdamK<float>& k) {
+  if (__builtin_bit_cast(uint16_t, from_f<T>(w)) != pb) w = to_f(__builtin_bit_cast(T, pb));
+  adam_elem<float>(w, to_f(__builtin_bit_cast(T, gb)), m, v, k);
+  pb = __builtin_bit_cast(uint16_t, from_f<T>(w));
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TR_THREADS)
+adam_master_kernel(const agn_adam_master_desc* __restrict__ descs, int ntensor, const int32_t* __restrict__ cmap,
+                   int nchunk, int dtype) {
+  const int t = threadIdx.x;
+  for (int c = blockIdx.x; c < nchunk; c += gridDim.x) {  // block-uniform walk of the chunk map
+    const int ti = cmap[2 * c], ci = cmap[2 * c + 1];
+    if (ti < 0 || ti >= ntensor || ci < 0) continue;     // a malformed map entry touches nothing
+    const agn_adam_master_desc d = descs[ti];
+    if (d.dtype != dtype || !d.p || !d.g || !d.w || !d.m || !d.v) continue;
+    const int64_t e0 = (int64_t)ci * ADAM_CHUNK;
+    if (e0 >= d.n) continue;                              // n == 0: a parameter without a gradient
+    const int len = (int)min((int64_t)ADAM_CHUNK, d.n - e0);
+    const AdamK<float> k = adam_scalars<float>(d);
+    uint16_t* p = (uint16_t*)d.p + e0;
+    const uint16_t* g = (const uint16_t*)d.g + e0;
+    float* w = (float*)d.w + e0;
+    float* m = (float*)d.m + e0;
+    float* v = (float*)d.v + e0;
+    // e0 * 2 is a multiple of 16, so the chunk is aligned exactly when the tensor is
+    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(w) |
+                       reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    const int nv = vec ? len / MW : 0;
+    for (int i = t; i < nv; i += TR_THREADS) {
+      u16x8 pv = reinterpret_cast<u16x8*>(p)[i];
+      const u16x8 gv = reinterpret_cast<const u16x8*>(g)[i];
+      f32x4 wv[2], mv[2], vv[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        wv[h] = reinterpret_cast<f32x4*>(w)[2 * i + h];
+        mv[h] = reinterpret_cast<f32x4*>(m)[2 * i + h];
+        vv[h] = reinterpret_cast<f32x4*>(v)[2 * i + h];
+      }
+#pragma unroll
+      for (int q = 0; q < MW; ++q) {
+        uint16_t pb = pv[q];
+        float we = wv[q / 4][q % 4], me = mv[q / 4][q % 4], ve = vv[q / 4][q % 4];
+        adam_master_elem<T>(pb, gv[q], we, me, ve, k);
+        pv[q] = pb; wv[q / 4][q % 4] = we; mv[q / 4][q % 4] = me; vv[q / 4][q % 4] = ve;
+      }
+      reinterpret_cast<u16x8*>(p)[i] = pv;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        reinterpret_cast<f32x4*>(w)[2 * i + h] = wv[h];
+        reinterpret_cast<f32x4*>(m)[2 * i + h] = mv[h];
+        reinterpret_cast<f32x4*>(v)[2 * i + h] = vv[h];
+      }
+    }
+    for (int i = nv * MW + t; i < len; i += TR_THREADS) adam_master_elem<T>(p[i], g[i], w[i], m[i], v[i], k);
   }
 }
 
@@ -244,6 +323,23 @@ int agn_adam_step(const agn_adam_desc* descs_device, int ntensor, const int32_t*
                        nchunk, dtype);
   else
     hipLaunchKernelGGL(adam_kernel<double>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor,
+                       chunk_map_device, nchunk, dtype);
+  return launch_status();
+}
+
+int agn_adam_step_master(const agn_adam_master_desc* descs_device, int ntensor, const int32_t* chunk_map_device,
+                         int nchunk, int dtype, void* stream) {
+  if (ntensor < 0 || nchunk < 0) return AGN_E_ARG;
+  if (dtype != AGN_BF16 && dtype != AGN_F16) return AGN_E_DTYPE;
+  if (ntensor == 0 || nchunk == 0) return 0;
+  if (!descs_device || !chunk_map_device) return AGN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = nchunk < ADAM_MAX_BLOCKS ? nchunk : ADAM_MAX_BLOCKS;
+  if (dtype == AGN_BF16)
+    hipLaunchKernelGGL(adam_master_kernel<bf16>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor,
+                       chunk_map_device, nchunk, dtype);
+  else
+    hipLaunchKernelGGL(adam_master_kernel<f16>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor,
                        chunk_map_device, nchunk, dtype);
   return launch_status();
 }

@@ -739,6 +739,41 @@ int agn_adam_chunk_elems(void);
 int agn_adam_step(const agn_adam_desc* descs_device, int ntensor, const int32_t* chunk_map_device, int nchunk,
                   int dtype, void* stream);
 
+/* agn_adam_step_master: the same step for 16-bit parameters with fp32 master weights. The reference's
+ * `precision: bf16` / `float16` sets the default dtype (train.py:30-38), so the model's parameters are
+ * 16-bit, and steps them with torch.optim.Adam (train.py:207-212), whose 16-bit p, exp_avg and exp_avg_sq
+ * round most updates away. Here every tensor of dtype `dtype` (AGN_BF16 or AGN_F16: of p and g) has an
+ * fp32 master copy w and fp32 moments m, v. Per element, in this order, every fp32 operation rounded
+ * once and nothing fused (T = the 16-bit type, round_T = RNE):
+ *     w  = (bits(round_T(w)) == bits(p)) ? w : (float)p     the master follows the parameter
+ *     g' = (float)g + weight_decay * w                       (only when weight_decay != 0)
+ *     m, v, w updated as agn_adam_step updates (m, v, p) of an fp32 tensor from g'
+ *     p  = round_T(w)
+ *   So (w, m, v) are bitwise what agn_adam_step gives on fp32 tensors (w, (float)g, m, v): weight decay
+ *   and the update read the master, never p. An element whose p was written since the last step (a
+ *   load_state_dict, a copy_) restarts from (float)p and keeps its moments; the comparison is on the
+ *   16-bit patterns, so +-0 and NaN need no case of their own.
+ *   The table, the chunk map (E = agn_adam_chunk_elems), the 2048-block cap and the skipped entries (n == 0,
+ *   a null pointer, another dtype, a map entry outside the table or past the tensor's end) are
+ *   agn_adam_step's. 8 elements per thread (16 B of p and g, 2 x 16 B of w, m, v) where a tensor's five
+ *   pointers are 16-B aligned (scalar tail), scalar otherwise.
+ *   Errors: AGN_E_ARG (a null table or map, a negative count), AGN_E_DTYPE (not AGN_BF16 / AGN_F16). */
+typedef struct {
+  void* p;            /* parameter (bf16 / fp16), n elements, updated in place */
+  const void* g;      /* gradient, p's dtype */
+  void* w;            /* fp32 master copy of p, updated in place */
+  void* m;            /* exp_avg (fp32), updated in place */
+  void* v;            /* exp_avg_sq (fp32), updated in place */
+  int64_t n;
+  int dtype;          /* AGN_BF16 / AGN_F16, of p and g */
+  int _pad;
+  double beta1, beta2, eps, weight_decay;
+  double step_size;   /* lr / (1 - beta1^t) */
+  double bc2_sqrt;    /* sqrt(1 - beta2^t) */
+} agn_adam_master_desc;
+int agn_adam_step_master(const agn_adam_master_desc* descs_device, int ntensor, const int32_t* chunk_map_device,
+                         int nchunk, int dtype, void* stream);
+
 /* ---- training-mode dropout of the MLP chains (mlp.py:40-51 `x = dropout(act(layer(x)))`),
  * csrc/dropout.hip: activation + dropout over a contiguous tensor of n elements taken
  * flat, dtype AGN_F32 / AGN_BF16 / AGN_F16 / AGN_F64 (fp64 computes in double, the others in float).

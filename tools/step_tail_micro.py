@@ -13,6 +13,11 @@ is also timed with HIP events over repeated launches from the optimizer's own ta
 bytes/s against the 28 B per parameter the update moves (p, m, v read and written, g read, fp32).
 
   python tools/step_tail_micro.py [--windows 5]            timings; the last line is one JSON object
+  python tools/step_tail_micro.py --master                 the C3 parameter set in bf16: torch.optim.Adam on the
+      bf16 parameters (what aerognn.optim.Adam runs for them without the flag) against
+      aerognn.optim.Adam(master_weights=True), same method; agn_adam_step_master alone against the 30 B per
+      parameter it moves (p, g 2 B and w, m, v 4 B read; p, w, m, v written). With --launch-counts: the
+      launches of these two
   python tools/step_tail_micro.py --launch-counts          kernel launches per call of each tail, from
       rocprofv3 --kernel-trace --stats runs of this file's --child mode (two lengths per tail; the
       difference of the traces' kernel counts over the difference in calls)
@@ -71,12 +76,12 @@ def param_shapes(which):
     return [tuple(p.shape) for p in m.parameters()]
 
 
-def make_optimizer(cls, shapes):
+def make_optimizer(cls, shapes, dtype=torch.float32, **kw):
     g = torch.Generator(device=dev).manual_seed(1)
-    ps = [torch.nn.Parameter(torch.randn(s, device=dev, generator=g)) for s in shapes]
+    ps = [torch.nn.Parameter(torch.randn(s, device=dev, generator=g).to(dtype)) for s in shapes]
     for p in ps:
-        p.grad = torch.randn(p.shape, device=dev, generator=g) * 1e-2
-    return cls(ps, lr=1e-3), ps
+        p.grad = (torch.randn(p.shape, device=dev, generator=g) * 1e-2).to(dtype)
+    return cls(ps, lr=1e-3, **kw), ps
 
 
 def windows(fns, nwin, min_s=0.5):
@@ -113,14 +118,16 @@ def windows(fns, nwin, min_s=0.5):
     return [statistics.median(o) for o in out], [(min(o), max(o)) for o in out]
 
 
-def kernel_only(opt, iters=200):
-    """ms per agn_adam_step launch from the optimizer's float32 table (HIP events)."""
-    tab = [t for t in opt._agn_tables.values() if t.dtype == torch.float32][0]
+def kernel_only(opt, iters=200, dtype=torch.float32):
+    """ms per launch of agn_adam_step (agn_adam_step_master for a 16-bit table) from the optimizer's table
+    of `dtype` (HIP events)."""
+    tab = [t for t in opt._agn_tables.values() if t.dtype == dtype][0]
     lib = _lib.lib()
+    fn = lib.agn_adam_step_master if tab.master else lib.agn_adam_step
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def run():
-        rc = lib.agn_adam_step(tab.dev.data_ptr(), tab.nt, tab.cmap.data_ptr(), tab.nchunk, tab.code, st)
+        rc = fn(tab.dev.data_ptr(), tab.nt, tab.cmap.data_ptr(), tab.nchunk, tab.code, st)
         assert rc == 0, rc
     for _ in range(10):
         run()
@@ -151,9 +158,9 @@ def mse_pair(n, f, dtype):
 
 def tails():
     """name -> a callable that builds (and returns) one tail's step function."""
-    def adam(cls, which):
+    def adam(cls, which, dtype=torch.float32, **kw):
         def build():
-            opt, _ = make_optimizer(cls, param_shapes(which))
+            opt, _ = make_optimizer(cls, param_shapes(which), dtype, **kw)
             return opt.step
         return build
 
@@ -161,6 +168,8 @@ def tails():
         return lambda: mse_pair(n, f, dtype)[i]
     return {"adam_torch_c3": adam(torch.optim.Adam, "c3"), "adam_ours_c3": adam(agn_optim.Adam, "c3"),
             "adam_torch_airfoil": adam(torch.optim.Adam, "airfoil"), "adam_ours_airfoil": adam(agn_optim.Adam, "airfoil"),
+            "adam_torch_c3_bf16": adam(torch.optim.Adam, "c3", torch.bfloat16),
+            "adam_master_c3_bf16": adam(agn_optim.Adam, "c3", torch.bfloat16, master_weights=True),
             "mse_torch_5000x4_f32": mse(5000, 4, torch.float32, 0), "mse_ours_5000x4_f32": mse(5000, 4, torch.float32, 1),
             "mse_torch_1Mx4_bf16": mse(1000000, 4, torch.bfloat16, 0), "mse_ours_1Mx4_bf16": mse(1000000, 4, torch.bfloat16, 1)}
 
@@ -196,10 +205,30 @@ def launch_counts(names):
     return res
 
 
+def master(nwin):
+    """The C3 parameter set in bf16: torch's step on the bf16 parameters against the master-weight step."""
+    shapes = param_shapes("c3")
+    nparam = sum(int(torch.Size(s).numel()) for s in shapes)
+    ot, _ = make_optimizer(torch.optim.Adam, shapes, torch.bfloat16)
+    om, _ = make_optimizer(agn_optim.Adam, shapes, torch.bfloat16, master_weights=True)
+    (tt, tm), spread = windows([ot.step, om.step], nwin)
+    kms, nchunk = kernel_only(om, dtype=torch.bfloat16)
+    gbs = 30.0 * nparam / (kms * 1e-3) / 1e9
+    res = {"adam_master_c3_bf16": {"tensors": len(shapes), "params": nparam, "torch_bf16_us": tt * 1e6, "master_us": tm * 1e6,
+                                   "torch_over_master": tt / tm, "torch_minmax_us": [x * 1e6 for x in spread[0]],
+                                   "master_minmax_us": [x * 1e6 for x in spread[1]], "kernel_us": kms * 1e3,
+                                   "kernel_GBps": gbs, "chunks": nchunk}}
+    print(f"adam c3 bf16: {len(shapes)} tensors, {nparam} parameters: torch on the bf16 parameters {tt * 1e6:.1f} us/step, "
+          f"master weights {tm * 1e6:.1f} us/step (x{tt / tm:.2f}); agn_adam_step_master alone {kms * 1e3:.1f} us = "
+          f"{gbs:.0f} GB/s of 30 B/parameter ({nchunk} chunks)", flush=True)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--launch-counts", action="store_true")
+    ap.add_argument("--master", action="store_true")
     ap.add_argument("--child")
     ap.add_argument("--calls", type=int, default=4)
     a = ap.parse_args()
@@ -208,8 +237,11 @@ def main():
     if a.child:
         return child(a.child, a.calls)
     if a.launch_counts:
-        print(json.dumps({"launches_per_call": launch_counts(sorted(tails()))}), flush=True)
+        names = [n for n in sorted(tails()) if n.endswith("_c3_bf16") == a.master]
+        print(json.dumps({"launches_per_call": launch_counts(names)}), flush=True)
         return
+    if a.master:
+        return master(a.windows)
     res = {}
     for which in ("c3", "airfoil"):
         shapes = param_shapes(which)
