@@ -56,7 +56,8 @@ LAUNCHES = ("agn_pack", "agn_mlp_forward", "agn_mlp_backward", "agn_reduce_parti
             "agn_edge_forward32", "agn_edge_agg_fixup",
             "agn_proj_forward", "agn_proj_backward", "agn_fourier_embed", "agn_fourier_embed_bwd", "agn_eval_sums",
             "agn_aero_forces", "agn_surface_forces", "agn_face_edges", "agn_mse_loss", "agn_adam_step", "agn_adam_step_master",
-            "agn_act_dropout_fwd", "agn_act_dropout_bwd")
+            "agn_act_dropout_fwd", "agn_act_dropout_bwd", "agn_mse_loss_scaled", "agn_grad_check", "agn_adam_step_scaled",
+            "agn_adam_step_master_scaled", "agn_loss_scale_update")
 
 
 class _Lib:

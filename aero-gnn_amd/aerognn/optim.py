@@ -36,6 +36,19 @@ RuntimeError, and the options this module does not cover raise ValueError, at co
 load_state_dict() keeps the three tensors fp32 (torch's casts state to the parameter's dtype), upcasts
 the 16-bit moments of a plain run's checkpoint, and keeps the optimizer's own master_weights flag when the
 checkpoint's groups have none.
+
+Loss scaling. `step(scaler=s)` (what aerognn.train.LossScaler.step(optimizer) calls; step() without it is
+unchanged) is the step on scaled gradients, in two phases so that no tensor of any table moves unless every
+gradient is finite: first every table's descriptors are written and copied, then agn_grad_check reads every
+table's gradients and sets the scaler's found_inf flag on the device, then agn_adam_step_scaled /
+agn_adam_step_master_scaled run, which return at once when the flag is set and otherwise multiply each
+gradient by (float)(1 / S) in front of the unscaled step. Nothing falls back to torch's step, which would
+apply the scaled gradients: a parameter with a gradient that does not qualify here (16-bit without
+master_weights, CPU, non-contiguous), a closure and an uncovered option raise RuntimeError. The `step`
+counters stay on the host, and the host never waits for the step it enqueues: they are incremented as
+always, a copy of found_inf to a page-locked word is enqueued behind the check and guarded by an event, and
+the NEXT step() (and state_dict() / load_state_dict()) waits for that event and takes the increments of a
+skipped step back, by which time the next forward and backward are queued behind it.
 """
 from __future__ import annotations
 
@@ -158,6 +171,24 @@ def _master_state(p, st):
             st[k] = t.detach().to(device=p.device, dtype=torch.float32).contiguous()
 
 
+class _PendingStep:
+    """A scaled step whose found_inf copy may still be in flight: the `step` tensors it incremented, the
+    page-locked word the flag is copied to and the event behind the copy."""
+
+    def __init__(self, word, event, steps, done):
+        self.word, self.event, self.steps, self.done = word, event, steps, done
+
+    def resolve(self):
+        """Wait for the copy; a skipped step does not count."""
+        if self.steps is None:
+            return
+        self.event.synchronize()
+        if int(self.word[0]) != 0:
+            torch._foreach_sub_(self.steps, 1)
+        self.steps = None
+        self.done(self)
+
+
 class Adam(_TorchAdam):
     """torch.optim.Adam whose step() runs on agn_adam_step where it applies (module docstring).
     `replay = False` (class or instance) partitions the parameters afresh at every step (measurements)."""
@@ -255,8 +286,21 @@ class Adam(_TorchAdam):
                 return False
         return True
 
+    def _resolve_pending(self):
+        pend = self.__dict__.get("_agn_pending")
+        if pend is not None:
+            pend.resolve()
+            self._agn_pending = None
+
+    def state_dict(self):
+        self._resolve_pending()  # the counters of a skipped scaled step are taken back first
+        return super().state_dict()
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, *, scaler=None):
+        self._resolve_pending()
+        if scaler is not None:
+            return self._scaled_step(closure, scaler)
         if not self._check_master(closure) and (closure is not None or not self._covered()):
             return _base_step(self, closure)
         plan = self.__dict__.get("_agn_plan") if self.replay else None
@@ -290,6 +334,45 @@ class Adam(_TorchAdam):
         self._device_step(ours, keep_plan=not rest)
         return None
 
+    def _scaled_step(self, closure, scaler):
+        """step(scaler=...): module docstring, "Loss scaling". Everything that would run torch's own step
+        raises before anything is changed."""
+        if closure is not None:
+            raise RuntimeError("aerognn.optim.Adam: a loss-scaled step does not take a closure: step(closure) runs "
+                               "torch's own step, which would apply the scaled gradients")
+        self._check_master(None)
+        for gi, g in enumerate(self.param_groups):
+            bad = self._uncovered(g)
+            if bad:
+                raise RuntimeError(f"aerognn.optim.Adam: a loss-scaled step cannot be combined with {bad} (param "
+                                   f"group {gi}): that setting runs torch's own step, which would apply the scaled "
+                                   "gradients")
+        plan = self.__dict__.get("_agn_plan") if self.replay else None
+        if plan is not None:
+            work = self._replay(plan)
+            if work is not None:
+                self._scaled_launch(work, scaler)
+                return None
+            self._agn_plan = None
+        ours, rest = [], False
+        for gi, g in enumerate(self.param_groups):
+            master = bool(g.get("master_weights"))
+            for i, p in enumerate(g["params"]):
+                if self._qualifies(p, gi, master):
+                    ours.append((p, gi))
+                elif p.grad is not None:
+                    name = repr(g["param_names"][i]) if "param_names" in g else f"{i}"
+                    raise RuntimeError(f"aerognn.optim.Adam: parameter {name} of group {gi} ({p.dtype} on {p.device}, "
+                                       f"shape {tuple(p.shape)}) cannot take the loss-scaled step on the device "
+                                       "(a 16-bit parameter needs master_weights=True; a parameter must be a "
+                                       "contiguous HIP tensor with a dense gradient of its dtype), and torch's own "
+                                       "step would apply the scaled gradient")
+                else:
+                    rest = True
+        if ours:
+            self._device_step(ours, keep_plan=not rest, scaler=scaler)
+        return None
+
     def _replay(self, plan):
         """The steady state: the parameter list, its storage, its entries in self.state and their tensors
         are those of the last step (checked one by one, before anything is changed), so only the
@@ -321,7 +404,7 @@ class Adam(_TorchAdam):
             work.append((tab, recs, grads))
         return work
 
-    def _device_step(self, ours, keep_plan):
+    def _device_step(self, ours, keep_plan, scaler=None):
         tables = self.__dict__.setdefault("_agn_tables", {})
         by_key = {}
         for p, gi in ours:
@@ -333,8 +416,11 @@ class Adam(_TorchAdam):
                 tab = tables[(device, dtype)] = _Table(device, dtype)
             with torch.cuda.device(device):
                 recs = self._records(tab, items)
-                self._launch(tab, recs, [r[0].grad for r in recs])
+                if scaler is None:
+                    self._launch(tab, recs, [r[0].grad for r in recs])
             planned.append((tab, recs))
+        if scaler is not None:  # every table has its state and its records: check all, then step all
+            self._scaled_launch([(tab, recs, [r[0].grad for r in recs]) for tab, recs in planned], scaler)
         # replayed only when every parameter runs here and has its state (none without a gradient so far)
         if keep_plan and all(r[2] is not None for _, recs in planned for r in recs):
             self._agn_plan = (self.state, sum(len(g["params"]) for g in self.param_groups),
@@ -366,10 +452,42 @@ class Adam(_TorchAdam):
             tab.rebuild(sig, *([r[k] for r in recs] for k in (3, 4, 5, 6, 7)))
         return recs
 
+    def _scaled_launch(self, work, scaler):
+        """The two phases of a loss-scaled step over `work` = [(table, records, gradients)]."""
+        state = scaler._device_state(work[0][0].device)
+        for tab, _, _ in work:
+            if tab.device != state.device:
+                raise RuntimeError(f"aerognn.optim.Adam: the LossScaler's state is on {state.device}, a parameter "
+                                   f"table on {tab.device}")
+        sp, lib = state.data_ptr(), L.lib()
+        from .core import stream
+        with torch.cuda.device(state.device):
+            fired, steps = [], []
+            for tab, recs, grads in work:
+                live = self._fill(tab, recs, grads)
+                if live:
+                    fired.append((tab, recs, live))
+                    steps += [recs[i][2]["step"] for i in live]
+            if not fired:
+                return
+            for tab, _, _ in fired:
+                L.check(lib.agn_grad_check(tab.dev.data_ptr(), int(tab.master), tab.nt, tab.cmap.data_ptr(), tab.nchunk,
+                                           tab.code, sp, stream()), "grad_check")
+            self._agn_pending = scaler._watch(steps)
+            for tab, recs, live in fired:
+                self._fire(tab, recs, live, sp)
+
     def _launch(self, tab, recs, grads):
+        live = self._fill(tab, recs, grads)
+        if live:
+            self._fire(tab, recs, live)
+
+    def _fill(self, tab, recs, grads):
+        """The host half of a table's step: the counters of the tensors with a gradient go up by one, their
+        descriptors are written and the copy is enqueued. Returns their indices (empty: nothing to run)."""
         live = [i for i, g in enumerate(grads) if g is not None]
         if not live:
-            return
+            return live
         steps = [recs[i][2]["step"] for i in live]
         torch._foreach_add_(steps, 1)
         ts = torch.stack(steps).tolist()
@@ -396,10 +514,19 @@ class Adam(_TorchAdam):
         h["n"][li] = [recs[i][6] for i in live]
         h["g"][li] = [grads[i].data_ptr() for i in live]
         tab.commit()
+        return live
+
+    def _fire(self, tab, recs, live, scale_state=None):
+        """The launch over a committed table; scale_state: the device address of a LossScaler's state."""
         from .core import stream
-        fn = L.lib().agn_adam_step_master if tab.master else L.lib().agn_adam_step
-        L.check(fn(tab.dev.data_ptr(), tab.nt, tab.cmap.data_ptr(), tab.nchunk, tab.code, stream()),
-                "adam_step_master" if tab.master else "adam_step")
+        lib = L.lib()
+        args = (tab.dev.data_ptr(), tab.nt, tab.cmap.data_ptr(), tab.nchunk, tab.code)
+        if scale_state is None:
+            fn = lib.agn_adam_step_master if tab.master else lib.agn_adam_step
+            L.check(fn(*args, stream()), "adam_step_master" if tab.master else "adam_step")
+        else:
+            fn = lib.agn_adam_step_master_scaled if tab.master else lib.agn_adam_step_scaled
+            L.check(fn(*args, scale_state, stream()), "adam_step_master_scaled" if tab.master else "adam_step_scaled")
         _bump_versions([recs[i][0] for i in live])
 
     def add_param_group(self, param_group):
@@ -411,6 +538,7 @@ class Adam(_TorchAdam):
         `state_dict` itself: torch casts every floating state tensor but `step` to the parameter's dtype
         (through a call bound to Optimizer, which a subclass cannot replace). A group that had
         master_weights keeps it when the checkpoint's group has no such key (a plain run's)."""
+        self._resolve_pending()
         had = [g.get("master_weights") for g in self.param_groups]
         super().load_state_dict(state_dict)
         for g, flag, saved in zip(self.param_groups, had, state_dict["param_groups"]):

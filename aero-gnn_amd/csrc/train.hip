@@ -24,6 +24,14 @@
 // w = (bits(round_T(w)) == bits(p)) ? w : (float)p, then adam_elem<float> on (w, (float)g, m, v) exactly
 // as agn_adam_step runs it on an fp32 tensor, then p = round_T(w). 8 elements per thread where the
 // five pointers are 16-B aligned (one 16-B access for p and g, two for w, m, v), scalar otherwise.
+//
+// Loss scaling (the reference's `precision: float16`, train.py:35-38): a 16-byte agn_loss_scale_state in
+// device memory holds the scale S, the found_inf flag, the growth tracker and the skipped-step count.
+// agn_mse_loss_scaled multiplies the fp64 gradient by S before its one rounding chain; agn_grad_check reads
+// every live gradient of a table once (exponent bits all ones = inf / NaN) and sets found_inf;
+// agn_adam_step_scaled / agn_adam_step_master_scaled are the two Adam kernels with g * (float)(1 / S) in front of
+// adam_elem, and return at once when found_inf is set; agn_loss_scale_update is torch._amp_update_scale_ on
+// the state, by one thread. The unscaled entry points launch the same templates without a state.
 #include "common.hpp"
 #include "host.hpp"
 #include "aerognn.h"
@@ -60,8 +68,10 @@ template <> AGN_DEV float round_from_f64<float>(double v) { return (float)v; }
 template <typename T, typename TY>
 __global__ void __launch_bounds__(TR_THREADS)
 mse_chunk_kernel(int n, int f, const T* __restrict__ pred, int pred_ld, const TY* __restrict__ y, int y_ld,
-                 double n_global, T* __restrict__ dpred, int dpred_ld, double* __restrict__ part) {
+                 double n_global, T* __restrict__ dpred, int dpred_ld, double* __restrict__ part,
+                 const agn_loss_scale_state* __restrict__ state) {
   __shared__ double sh[TR_THREADS];
+  const double scale = state ? (double)state->scale : 1.0;
   const int t = threadIdx.x;
   const int64_t r0 = (int64_t)blockIdx.x * MSE_ROWS;
   const int rows = (int)min((int64_t)MSE_ROWS, (int64_t)n - r0);  // >= 1: the grid is ceil(n / MSE_ROWS)
@@ -72,7 +82,11 @@ mse_chunk_kernel(int n, int f, const T* __restrict__ pred, int pred_ld, const TY
     const size_t row = (size_t)(r0 + r);
     const double d = (double)pred[row * pred_ld + j] - (double)y[row * y_ld + j];
     s += d * d;
-    if (dpred) dpred[row * dpred_ld + j] = round_from_f64<T>((2.0 * d) / n_global);
+    if (dpred) {
+      double q = (2.0 * d) / n_global;
+      if (state) q = q * scale;  // before the rounding to T: what T cannot hold unscaled survives
+      dpred[row * dpred_ld + j] = round_from_f64<T>(q);
+    }
   }
   s = block_tree_sum(s, sh, t);
   if (t == 0) part[blockIdx.x] = s;
@@ -96,10 +110,10 @@ mse_finish_kernel(int nchunk, const double* __restrict__ part, double n_global, 
 
 template <typename T, typename TY>
 void launch_mse(int n, int f, const void* pred, int pred_ld, const void* y, int y_ld, double n_global, void* dpred,
-                int dpred_ld, double* part, hipStream_t st) {
+                int dpred_ld, double* part, const agn_loss_scale_state* state, hipStream_t st) {
   const int nchunk = (int)(((int64_t)n + MSE_ROWS - 1) / MSE_ROWS);
   hipLaunchKernelGGL((mse_chunk_kernel<T, TY>), dim3(nchunk), dim3(TR_THREADS), 0, st, n, f, (const T*)pred, pred_ld,
-                     (const TY*)y, y_ld, n_global, (T*)dpred, dpred_ld, part);
+                     (const TY*)y, y_ld, n_global, (T*)dpred, dpred_ld, part, state);
 }
 
 // ---------------------------------------------------------------------------- Adam
@@ -151,13 +165,23 @@ template <> struct Vec16<float> { typedef f32x4 type; static constexpr int W = 4
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 template <> struct Vec16<double> { typedef f64x2 type; static constexpr int W = 2; };
 
-template <typename T>
+// SC: the loss-scaled step. found_inf set: nothing is touched; else g * inv in front of adam_elem, one
+// rounding in T, inv = (float)(1 / (double)S) as torch.amp.GradScaler forms it
+template <bool SC, typename T>
+AGN_DEV T unscaled(T g, T inv) { return SC ? g * inv : g; }
+
+template <typename T, bool SC>
 __global__ void __launch_bounds__(TR_THREADS)
 adam_kernel(const agn_adam_desc* __restrict__ descs, int ntensor, const int32_t* __restrict__ cmap, int nchunk,
-            int dtype) {
+            int dtype, const agn_loss_scale_state* __restrict__ state) {
   typedef typename Vec16<T>::type V;
   constexpr int W = Vec16<T>::W;
   const int t = threadIdx.x;
+  T inv = (T)1;
+  if (SC) {
+    if (state->found_inf != 0) return;
+    inv = (T)(float)(1.0 / (double)state->scale);
+  }
   for (int c = blockIdx.x; c < nchunk; c += gridDim.x) {  // block-uniform walk of the chunk map
     const int ti = cmap[2 * c], ci = cmap[2 * c + 1];
     if (ti < 0 || ti >= ntensor || ci < 0) continue;     // a malformed map entry touches nothing
@@ -181,14 +205,14 @@ adam_kernel(const agn_adam_desc* __restrict__ descs, int ntensor, const int32_t*
 #pragma unroll
       for (int q = 0; q < W; ++q) {
         T pe = pv[q], me = mv[q], ve = vv[q];
-        adam_elem<T>(pe, gv[q], me, ve, k);
+        adam_elem<T>(pe, unscaled<SC, T>(gv[q], inv), me, ve, k);
         pv[q] = pe; mv[q] = me; vv[q] = ve;
       }
       reinterpret_cast<V*>(p)[i] = pv;
       reinterpret_cast<V*>(m)[i] = mv;
       reinterpret_cast<V*>(v)[i] = vv;
     }
-    for (int i = nv * W + t; i < len; i += TR_THREADS) adam_elem<T>(p[i], g[i], m[i], v[i], k);
+    for (int i = nv * W + t; i < len; i += TR_THREADS) adam_elem<T>(p[i], unscaled<SC, T>(g[i], inv), m[i], v[i], k);
   }
 }
 
@@ -199,18 +223,24 @@ constexpr int MW = 8;  // elements per thread on the wide path: 16 B of p and of
 // one element: pb / gb are the 16-bit patterns of p and g (T = bf16 or f16). The master follows the
 // parameter: an element whose p is not round_T(w) (something wrote p since the last step) restarts from
 // (float)p and keeps its moments; the patterns are compared, so +-0 and NaN need no case of their own.
-template <typename T>
-AGN_DEV void adam_master_elem(uint16_t& pb, uint16_t gb, float& w, float& m, float& v, const AdamK<float>& k) {
+template <typename T, bool SC>
+AGN_DEV void adam_master_elem(uint16_t& pb, uint16_t gb, float& w, float& m, float& v, const AdamK<float>& k,
+                              float inv) {
   if (__builtin_bit_cast(uint16_t, from_f<T>(w)) != pb) w = to_f(__builtin_bit_cast(T, pb));
-  adam_elem<float>(w, to_f(__builtin_bit_cast(T, gb)), m, v, k);
+  adam_elem<float>(w, unscaled<SC, float>(to_f(__builtin_bit_cast(T, gb)), inv), m, v, k);
   pb = __builtin_bit_cast(uint16_t, from_f<T>(w));
 }
 
-template <typename T>
+template <typename T, bool SC>
 __global__ void __launch_bounds__(TR_THREADS)
 adam_master_kernel(const agn_adam_master_desc* __restrict__ descs, int ntensor, const int32_t* __restrict__ cmap,
-                   int nchunk, int dtype) {
+                   int nchunk, int dtype, const agn_loss_scale_state* __restrict__ state) {
   const int t = threadIdx.x;
+  float inv = 1.0f;
+  if (SC) {
+    if (state->found_inf != 0) return;
+    inv = (float)(1.0 / (double)state->scale);
+  }
   for (int c = blockIdx.x; c < nchunk; c += gridDim.x) {  // block-uniform walk of the chunk map
     const int ti = cmap[2 * c], ci = cmap[2 * c + 1];
     if (ti < 0 || ti >= ntensor || ci < 0) continue;     // a malformed map entry touches nothing
@@ -243,7 +273,7 @@ adam_master_kernel(const agn_adam_master_desc* __restrict__ descs, int ntensor, 
       for (int q = 0; q < MW; ++q) {
         uint16_t pb = pv[q];
         float we = wv[q / 4][q % 4], me = mv[q / 4][q % 4], ve = vv[q / 4][q % 4];
-        adam_master_elem<T>(pb, gv[q], we, me, ve, k);
+        adam_master_elem<T, SC>(pb, gv[q], we, me, ve, k, inv);
         pv[q] = pb; wv[q / 4][q % 4] = we; mv[q / 4][q % 4] = me; vv[q / 4][q % 4] = ve;
       }
       reinterpret_cast<u16x8*>(p)[i] = pv;
@@ -254,8 +284,180 @@ adam_master_kernel(const agn_adam_master_desc* __restrict__ descs, int ntensor, 
         reinterpret_cast<f32x4*>(v)[2 * i + h] = vv[h];
       }
     }
-    for (int i = nv * MW + t; i < len; i += TR_THREADS) adam_master_elem<T>(p[i], g[i], w[i], m[i], v[i], k);
+    for (int i = nv * MW + t; i < len; i += TR_THREADS)
+      adam_master_elem<T, SC>(p[i], g[i], w[i], m[i], v[i], k, inv);
   }
+}
+
+// ---------------------------------------------------------------------------- loss scaling: check and update
+AGN_DEV bool adam_entry_live(const agn_adam_desc& d) { return d.p && d.g && d.m && d.v; }
+AGN_DEV bool adam_entry_live(const agn_adam_master_desc& d) { return d.p && d.g && d.w && d.m && d.v; }
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+template <typename U> struct Chk16;  // 16 B of the element's bit pattern
+template <> struct Chk16<uint16_t> { typedef u16x8 type; };
+template <> struct Chk16<uint32_t> { typedef u32x4 type; };
+template <> struct Chk16<uint64_t> { typedef u64x2 type; };
+
+// Read-only pass over the gradients agn_adam_step / agn_adam_step_master would step: the same walk of the
+// chunk map and the same skipped entries. U: the element's bit pattern, EXP: its exponent field; all ones
+// there is +-inf or NaN. A thread that saw one stores the flag (every writer stores the same 1).
+template <typename D, typename U, U EXP>
+__global__ void __launch_bounds__(TR_THREADS)
+grad_check_kernel(const D* __restrict__ descs, int ntensor, const int32_t* __restrict__ cmap, int nchunk, int dtype,
+                  agn_loss_scale_state* __restrict__ state) {
+  typedef typename Chk16<U>::type V;
+  constexpr int W = 16 / (int)sizeof(U);
+  const int t = threadIdx.x;
+  bool bad = false;
+  for (int c = blockIdx.x; c < nchunk; c += gridDim.x) {  // block-uniform walk of the chunk map
+    const int ti = cmap[2 * c], ci = cmap[2 * c + 1];
+    if (ti < 0 || ti >= ntensor || ci < 0) continue;
+    const D d = descs[ti];
+    if (d.dtype != dtype || !adam_entry_live(d)) continue;
+    const int64_t e0 = (int64_t)ci * ADAM_CHUNK;
+    if (e0 >= d.n) continue;
+    const int len = (int)min((int64_t)ADAM_CHUNK, d.n - e0);
+    const U* g = (const U*)d.g + e0;
+    const int nv = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? len / W : 0;
+    for (int i = t; i < nv; i += TR_THREADS) {
+      const V gv = reinterpret_cast<const V*>(g)[i];
+#pragma unroll
+      for (int q = 0; q < W; ++q) bad |= (gv[q] & EXP) == EXP;
+    }
+    for (int i = nv * W + t; i < len; i += TR_THREADS) bad |= (g[i] & EXP) == EXP;
+  }
+  if (bad) state->found_inf = 1;
+}
+
+template <typename D>
+void launch_grad_check(const void* descs, int ntensor, const int32_t* cmap, int nchunk, int dtype,
+                       agn_loss_scale_state* state, hipStream_t st) {
+  const dim3 grid(nchunk < ADAM_MAX_BLOCKS ? nchunk : ADAM_MAX_BLOCKS), block(TR_THREADS);
+  const D* d = (const D*)descs;
+  switch (dtype) {
+    case AGN_F32:
+      hipLaunchKernelGGL((grad_check_kernel<D, uint32_t, 0x7f800000u>), grid, block, 0, st, d, ntensor, cmap, nchunk,
+                         dtype, state);
+      break;
+    case AGN_F64:
+      hipLaunchKernelGGL((grad_check_kernel<D, uint64_t, 0x7ff0000000000000ull>), grid, block, 0, st, d, ntensor, cmap,
+                         nchunk, dtype, state);
+      break;
+    case AGN_BF16:
+      hipLaunchKernelGGL((grad_check_kernel<D, uint16_t, (uint16_t)0x7f80>), grid, block, 0, st, d, ntensor, cmap,
+                         nchunk, dtype, state);
+      break;
+    default:
+      hipLaunchKernelGGL((grad_check_kernel<D, uint16_t, (uint16_t)0x7c00>), grid, block, 0, st, d, ntensor, cmap,
+                         nchunk, dtype, state);
+      break;
+  }
+}
+
+// torch._amp_update_scale_ (amp_update_scale_cuda_kernel) on the state, then the flag is cleared
+__global__ void loss_scale_update_kernel(agn_loss_scale_state* __restrict__ state, double growth, double backoff,
+                                         int interval) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (state->found_inf != 0) {
+    state->scale = (float)((double)state->scale * backoff);
+    state->growth_tracker = 0;
+    state->skipped = state->skipped + 1;
+  } else {
+    const int successful = state->growth_tracker + 1;
+    if (successful == interval) {
+      const float grown = (float)((double)state->scale * growth);
+      if (isfinite(grown)) state->scale = grown;
+      state->growth_tracker = 0;
+    } else {
+      state->growth_tracker = successful;
+    }
+  }
+  state->found_inf = 0;
+}
+
+int mse_loss_impl(int dtype, int y_dtype, int n, int f, const void* pred, int pred_ld, const void* y, int y_ld,
+                  double n_global, double* loss_out, double* acc, void* dpred, int dpred_ld, void* scratch,
+                  const agn_loss_scale_state* state, void* stream) {
+  if (n < 0) return AGN_E_ARG;
+  if (dtype != AGN_F32 && dtype != AGN_BF16 && dtype != AGN_F16 && dtype != AGN_F64) return AGN_E_DTYPE;
+  if (y_dtype != dtype && y_dtype != AGN_F32) return AGN_E_DTYPE;
+  // f <= 2^31 / MSE_ROWS keeps a chunk's element count in an int
+  if (f < 1 || f > (1 << 19) || pred_ld < f || y_ld < f || (dpred && dpred_ld < f)) return AGN_E_SHAPE;
+  if (!(n_global > 0.0)) return AGN_E_SHAPE;
+  if (!loss_out) return AGN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {  // loss 0, acc unchanged: a plain memset of the 8 bytes, no kernel
+    const hipError_t e = hipMemsetAsync(loss_out, 0, sizeof(double), st);
+    return e == hipSuccess ? 0 : (int)e;
+  }
+  if (!pred || !y || !scratch) return AGN_E_ARG;
+  double* part = reinterpret_cast<double*>(scratch);
+  const bool ysame = y_dtype == dtype;
+#define AGN_MSE(T, TY) launch_mse<T, TY>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, state, st)
+  switch (dtype) {
+    case AGN_F32: AGN_MSE(float, float); break;
+    case AGN_F64:
+      if (ysame) AGN_MSE(double, double);
+      else AGN_MSE(double, float);
+      break;
+    case AGN_BF16:
+      if (ysame) AGN_MSE(bf16, bf16);
+      else AGN_MSE(bf16, float);
+      break;
+    default:
+      if (ysame) AGN_MSE(f16, f16);
+      else AGN_MSE(f16, float);
+      break;
+  }
+#undef AGN_MSE
+  const int nchunk = (int)(((int64_t)n + MSE_ROWS - 1) / MSE_ROWS);
+  hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(TR_THREADS), 0, st, nchunk, part, n_global, loss_out, acc);
+  return launch_status();
+}
+
+// state == nullptr: the unscaled step
+int adam_step_impl(const agn_adam_desc* descs, int ntensor, const int32_t* cmap, int nchunk, int dtype,
+                   const agn_loss_scale_state* state, void* stream) {
+  if (ntensor < 0 || nchunk < 0) return AGN_E_ARG;
+  if (dtype != AGN_F32 && dtype != AGN_F64) return AGN_E_DTYPE;
+  if (ntensor == 0 || nchunk == 0) return 0;
+  if (!descs || !cmap) return AGN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(nchunk < ADAM_MAX_BLOCKS ? nchunk : ADAM_MAX_BLOCKS), block(TR_THREADS);
+#define AGN_ADAM(T, SC) \
+  hipLaunchKernelGGL((adam_kernel<T, SC>), grid, block, 0, st, descs, ntensor, cmap, nchunk, dtype, state)
+  if (dtype == AGN_F32) {
+    if (state) AGN_ADAM(float, true);
+    else AGN_ADAM(float, false);
+  } else {
+    if (state) AGN_ADAM(double, true);
+    else AGN_ADAM(double, false);
+  }
+#undef AGN_ADAM
+  return launch_status();
+}
+
+int adam_step_master_impl(const agn_adam_master_desc* descs, int ntensor, const int32_t* cmap, int nchunk, int dtype,
+                          const agn_loss_scale_state* state, void* stream) {
+  if (ntensor < 0 || nchunk < 0) return AGN_E_ARG;
+  if (dtype != AGN_BF16 && dtype != AGN_F16) return AGN_E_DTYPE;
+  if (ntensor == 0 || nchunk == 0) return 0;
+  if (!descs || !cmap) return AGN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(nchunk < ADAM_MAX_BLOCKS ? nchunk : ADAM_MAX_BLOCKS), block(TR_THREADS);
+#define AGN_ADAM(T, SC) \
+  hipLaunchKernelGGL((adam_master_kernel<T, SC>), grid, block, 0, st, descs, ntensor, cmap, nchunk, dtype, state)
+  if (dtype == AGN_BF16) {
+    if (state) AGN_ADAM(bf16, true);
+    else AGN_ADAM(bf16, false);
+  } else {
+    if (state) AGN_ADAM(f16, true);
+    else AGN_ADAM(f16, false);
+  }
+#undef AGN_ADAM
+  return launch_status();
 }
 
 }  // namespace
@@ -273,74 +475,61 @@ size_t agn_mse_loss_temp_bytes(int n, int f) {
 int agn_mse_loss(int dtype, int y_dtype, int n, int f, const void* pred, int pred_ld, const void* y, int y_ld,
                  double n_global, double* loss_out, double* acc, void* dpred, int dpred_ld, void* scratch,
                  void* stream) {
-  if (n < 0) return AGN_E_ARG;
-  if (dtype != AGN_F32 && dtype != AGN_BF16 && dtype != AGN_F16 && dtype != AGN_F64) return AGN_E_DTYPE;
-  if (y_dtype != dtype && y_dtype != AGN_F32) return AGN_E_DTYPE;
-  // f <= 2^31 / MSE_ROWS keeps a chunk's element count in an int
-  if (f < 1 || f > (1 << 19) || pred_ld < f || y_ld < f || (dpred && dpred_ld < f)) return AGN_E_SHAPE;
-  if (!(n_global > 0.0)) return AGN_E_SHAPE;
-  if (!loss_out) return AGN_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (n == 0) {  // loss 0, acc unchanged: a plain memset of the 8 bytes, no kernel
-    const hipError_t e = hipMemsetAsync(loss_out, 0, sizeof(double), st);
-    return e == hipSuccess ? 0 : (int)e;
-  }
-  if (!pred || !y || !scratch) return AGN_E_ARG;
-  double* part = reinterpret_cast<double*>(scratch);
-  const bool ysame = y_dtype == dtype;
-  switch (dtype) {
-    case AGN_F32: launch_mse<float, float>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st); break;
-    case AGN_F64:
-      if (ysame) launch_mse<double, double>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
-      else launch_mse<double, float>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
-      break;
-    case AGN_BF16:
-      if (ysame) launch_mse<bf16, bf16>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
-      else launch_mse<bf16, float>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
-      break;
-    default:
-      if (ysame) launch_mse<f16, f16>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
-      else launch_mse<f16, float>(n, f, pred, pred_ld, y, y_ld, n_global, dpred, dpred_ld, part, st);
-      break;
-  }
-  const int nchunk = (int)(((int64_t)n + MSE_ROWS - 1) / MSE_ROWS);
-  hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(TR_THREADS), 0, st, nchunk, part, n_global, loss_out, acc);
-  return launch_status();
+  return mse_loss_impl(dtype, y_dtype, n, f, pred, pred_ld, y, y_ld, n_global, loss_out, acc, dpred, dpred_ld, scratch,
+                       nullptr, stream);
+}
+
+int agn_mse_loss_scaled(int dtype, int y_dtype, int n, int f, const void* pred, int pred_ld, const void* y, int y_ld,
+                        double n_global, double* loss_out, double* acc, void* dpred, int dpred_ld, void* scratch,
+                        const agn_loss_scale_state* state_device, void* stream) {
+  return mse_loss_impl(dtype, y_dtype, n, f, pred, pred_ld, y, y_ld, n_global, loss_out, acc, dpred, dpred_ld, scratch,
+                       state_device, stream);
 }
 
 int agn_adam_chunk_elems(void) { return ADAM_CHUNK; }
 
 int agn_adam_step(const agn_adam_desc* descs_device, int ntensor, const int32_t* chunk_map_device, int nchunk,
                   int dtype, void* stream) {
-  if (ntensor < 0 || nchunk < 0) return AGN_E_ARG;
-  if (dtype != AGN_F32 && dtype != AGN_F64) return AGN_E_DTYPE;
-  if (ntensor == 0 || nchunk == 0) return 0;
-  if (!descs_device || !chunk_map_device) return AGN_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int grid = nchunk < ADAM_MAX_BLOCKS ? nchunk : ADAM_MAX_BLOCKS;
-  if (dtype == AGN_F32)
-    hipLaunchKernelGGL(adam_kernel<float>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor, chunk_map_device,
-                       nchunk, dtype);
-  else
-    hipLaunchKernelGGL(adam_kernel<double>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor,
-                       chunk_map_device, nchunk, dtype);
-  return launch_status();
+  return adam_step_impl(descs_device, ntensor, chunk_map_device, nchunk, dtype, nullptr, stream);
 }
 
 int agn_adam_step_master(const agn_adam_master_desc* descs_device, int ntensor, const int32_t* chunk_map_device,
                          int nchunk, int dtype, void* stream) {
-  if (ntensor < 0 || nchunk < 0) return AGN_E_ARG;
-  if (dtype != AGN_BF16 && dtype != AGN_F16) return AGN_E_DTYPE;
+  return adam_step_master_impl(descs_device, ntensor, chunk_map_device, nchunk, dtype, nullptr, stream);
+}
+
+int agn_adam_step_scaled(const agn_adam_desc* descs_device, int ntensor, const int32_t* chunk_map_device, int nchunk,
+                         int dtype, const agn_loss_scale_state* state_device, void* stream) {
+  if (!state_device) return AGN_E_ARG;
+  return adam_step_impl(descs_device, ntensor, chunk_map_device, nchunk, dtype, state_device, stream);
+}
+
+int agn_adam_step_master_scaled(const agn_adam_master_desc* descs_device, int ntensor,
+                                const int32_t* chunk_map_device, int nchunk, int dtype,
+                                const agn_loss_scale_state* state_device, void* stream) {
+  if (!state_device) return AGN_E_ARG;
+  return adam_step_master_impl(descs_device, ntensor, chunk_map_device, nchunk, dtype, state_device, stream);
+}
+
+int agn_grad_check(const void* descs_device, int master, int ntensor, const int32_t* chunk_map_device, int nchunk,
+                   int dtype, agn_loss_scale_state* state_device, void* stream) {
+  if (ntensor < 0 || nchunk < 0 || !state_device) return AGN_E_ARG;
+  if (dtype != AGN_F32 && dtype != AGN_F64 && dtype != AGN_BF16 && dtype != AGN_F16) return AGN_E_DTYPE;
   if (ntensor == 0 || nchunk == 0) return 0;
   if (!descs_device || !chunk_map_device) return AGN_E_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = nchunk < ADAM_MAX_BLOCKS ? nchunk : ADAM_MAX_BLOCKS;
-  if (dtype == AGN_BF16)
-    hipLaunchKernelGGL(adam_master_kernel<bf16>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor,
-                       chunk_map_device, nchunk, dtype);
-  else
-    hipLaunchKernelGGL(adam_master_kernel<f16>, dim3(grid), dim3(TR_THREADS), 0, st, descs_device, ntensor,
-                       chunk_map_device, nchunk, dtype);
+  if (master) launch_grad_check<agn_adam_master_desc>(descs_device, ntensor, chunk_map_device, nchunk, dtype,
+                                                      state_device, st);
+  else launch_grad_check<agn_adam_desc>(descs_device, ntensor, chunk_map_device, nchunk, dtype, state_device, st);
+  return launch_status();
+}
+
+int agn_loss_scale_update(agn_loss_scale_state* state_device, double growth_factor, double backoff_factor,
+                          int growth_interval, void* stream) {
+  if (!state_device) return AGN_E_ARG;
+  if (growth_interval < 1 || !(growth_factor > 0.0) || !(backoff_factor > 0.0)) return AGN_E_SHAPE;
+  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state_device, growth_factor,
+                     backoff_factor, growth_interval);
   return launch_status();
 }
 

@@ -774,6 +774,49 @@ typedef struct {
 int agn_adam_step_master(const agn_adam_master_desc* descs_device, int ntensor, const int32_t* chunk_map_device,
                          int nchunk, int dtype, void* stream);
 
+/* ---- dynamic loss scaling on the device (the reference's `precision: float16`, train.py:35-38, whose
+ * gradients are fp16: at n_global = 2^22, 2 d / n_global is under fp16's smallest subnormal for every
+ * |d| < 2^-4, so the unscaled dpred is mostly zeros). The state lives in device memory and no entry point
+ * here reads it back; S is applied inside the loss kernel, before the rounding to pred's dtype.
+ *
+ * agn_mse_loss_scaled: agn_mse_loss with dpred = round_T(((2 d) / n_global) * (double)S), the same rounding
+ *   chain (fp16 overflows to +-inf). *loss_out and *acc are not scaled. state_device == NULL gives
+ *   agn_mse_loss's bytes (agn_mse_loss is that call).
+ * agn_grad_check: a read-only pass over the gradients of every live entry of dtype `dtype` (AGN_F32 /
+ *   AGN_F64 / AGN_BF16 / AGN_F16) of an agn_adam_desc table (master == 0) or an agn_adam_master_desc table
+ *   (master != 0): found_inf = 1 if any element is +-inf or NaN, nothing is written otherwise. The chunk
+ *   map, the 2048-block cap, the grid-stride walk and the skipped entries are agn_adam_step's. 16-B loads
+ *   where g is 16-B aligned (scalar tail), scalar otherwise.
+ * agn_adam_step_scaled / agn_adam_step_master_scaled: agn_adam_step / agn_adam_step_master behind the flag.
+ *   found_inf != 0: every block returns before it touches anything. Otherwise per element
+ *   g' = g * inv, inv = (float)(1.0 / (double)S) as torch.amp.GradScaler forms it, rounded once in the
+ *   table's compute type (fp32 for AGN_F32 and the 16-bit tables, fp64 for AGN_F64), in front of the
+ *   weight-decay term; the rest is the unscaled step, which is these kernels without a state.
+ * agn_loss_scale_update: torch._amp_update_scale_ by one thread. found_inf != 0: scale = (float)(scale *
+ *   backoff_factor), growth_tracker = 0, ++skipped. Otherwise ++growth_tracker, and at growth_interval
+ *   scale = (float)(scale * growth_factor) if that is finite and growth_tracker = 0 either way. Then
+ *   found_inf = 0.
+ * Errors: AGN_E_ARG (a null table, map or state, a negative count; agn_mse_loss_scaled as agn_mse_loss),
+ *   AGN_E_DTYPE, AGN_E_SHAPE (growth_interval < 1, a factor <= 0). */
+typedef struct {
+  float   scale;           /* S */
+  int32_t found_inf;       /* set by agn_grad_check, cleared by agn_loss_scale_update */
+  int32_t growth_tracker;
+  int32_t skipped;         /* steps skipped so far */
+} agn_loss_scale_state;    /* 16 B, lives in device memory */
+int agn_mse_loss_scaled(int dtype, int y_dtype, int n, int f, const void* pred, int pred_ld, const void* y, int y_ld,
+                        double n_global, double* loss_out, double* acc, void* dpred, int dpred_ld, void* scratch,
+                        const agn_loss_scale_state* state_device, void* stream);
+int agn_grad_check(const void* descs_device, int master, int ntensor, const int32_t* chunk_map_device, int nchunk,
+                   int dtype, agn_loss_scale_state* state_device, void* stream);
+int agn_adam_step_scaled(const agn_adam_desc* descs_device, int ntensor, const int32_t* chunk_map_device, int nchunk,
+                         int dtype, const agn_loss_scale_state* state_device, void* stream);
+int agn_adam_step_master_scaled(const agn_adam_master_desc* descs_device, int ntensor,
+                                const int32_t* chunk_map_device, int nchunk, int dtype,
+                                const agn_loss_scale_state* state_device, void* stream);
+int agn_loss_scale_update(agn_loss_scale_state* state_device, double growth_factor, double backoff_factor,
+                          int growth_interval, void* stream);
+
 /* ---- training-mode dropout of the MLP chains (mlp.py:40-51 `x = dropout(act(layer(x)))`),
  * csrc/dropout.hip: activation + dropout over a contiguous tensor of n elements taken
  * flat, dtype AGN_F32 / AGN_BF16 / AGN_F16 / AGN_F64 (fp64 computes in double, the others in float).

@@ -18,6 +18,10 @@ bytes/s against the 28 B per parameter the update moves (p, m, v read and writte
       aerognn.optim.Adam(master_weights=True), same method; agn_adam_step_master alone against the 30 B per
       parameter it moves (p, g 2 B and w, m, v 4 B read; p, w, m, v written). With --launch-counts: the
       launches of these two
+  python tools/step_tail_micro.py --scaled                 the --master measurement in fp16 with a
+      aerognn.train.LossScaler attached: torch's step on the fp16 parameters, the master-weight step and
+      LossScaler.step(optimizer) + update() alternate in one run; agn_grad_check alone against the 2 B per
+      parameter it reads and agn_adam_step_master_scaled alone. With --launch-counts: the launches of the three
   python tools/step_tail_micro.py --launch-counts          kernel launches per call of each tail, from
       rocprofv3 --kernel-trace --stats runs of this file's --child mode (two lengths per tail; the
       difference of the traces' kernel counts over the difference in calls)
@@ -141,6 +145,48 @@ def kernel_only(opt, iters=200, dtype=torch.float32):
     return s.elapsed_time(e) / iters, tab.nchunk
 
 
+def scaled_step(opt):
+    """LossScaler.step(opt) + update(): what train() runs in optimizer.step()'s place. The growth interval is
+    out of reach, so the scale stays where it starts however long the windows run."""
+    scaler = agn_train.LossScaler(dev, growth_interval=2 ** 30)
+
+    def step():
+        scaler.step(opt)
+        scaler.update()
+    return step, scaler
+
+
+def scaled_kernels(opt, scaler, iters=200, dtype=torch.float16):
+    """ms per launch of agn_grad_check and of the scaled Adam kernel from the optimizer's table of `dtype`."""
+    tab = [t for t in opt._agn_tables.values() if t.dtype == dtype][0]
+    lib = _lib.lib()
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sp = scaler._device_state().data_ptr()
+    args = (tab.dev.data_ptr(), tab.nt, tab.cmap.data_ptr(), tab.nchunk, tab.code)
+    step = lib.agn_adam_step_master_scaled if tab.master else lib.agn_adam_step_scaled
+
+    def check():
+        rc = lib.agn_grad_check(args[0], int(tab.master), *args[1:], sp, st)
+        assert rc == 0, rc
+
+    def adam():
+        rc = step(*args, sp, st)
+        assert rc == 0, rc
+    out = []
+    for run in (check, adam):
+        for _ in range(10):
+            run()
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(iters):
+            run()
+        e.record()
+        torch.cuda.synchronize()
+        out.append(s.elapsed_time(e) / iters)
+    return out
+
+
 def mse_pair(n, f, dtype):
     g = torch.Generator(device=dev).manual_seed(2)
     pred = torch.randn(n, f, device=dev, generator=g).to(dtype).requires_grad_(True)
@@ -164,12 +210,21 @@ def tails():
             return opt.step
         return build
 
+    def scaled(which, dtype):
+        def build():
+            opt, _ = make_optimizer(agn_optim.Adam, param_shapes(which), dtype, master_weights=True)
+            return scaled_step(opt)[0]
+        return build
+
     def mse(n, f, dtype, i):
         return lambda: mse_pair(n, f, dtype)[i]
     return {"adam_torch_c3": adam(torch.optim.Adam, "c3"), "adam_ours_c3": adam(agn_optim.Adam, "c3"),
             "adam_torch_airfoil": adam(torch.optim.Adam, "airfoil"), "adam_ours_airfoil": adam(agn_optim.Adam, "airfoil"),
             "adam_torch_c3_bf16": adam(torch.optim.Adam, "c3", torch.bfloat16),
             "adam_master_c3_bf16": adam(agn_optim.Adam, "c3", torch.bfloat16, master_weights=True),
+            "adam_torch_c3_f16": adam(torch.optim.Adam, "c3", torch.float16),
+            "adam_master_c3_f16": adam(agn_optim.Adam, "c3", torch.float16, master_weights=True),
+            "adam_scaled_c3_f16": scaled("c3", torch.float16),
             "mse_torch_5000x4_f32": mse(5000, 4, torch.float32, 0), "mse_ours_5000x4_f32": mse(5000, 4, torch.float32, 1),
             "mse_torch_1Mx4_bf16": mse(1000000, 4, torch.bfloat16, 0), "mse_ours_1Mx4_bf16": mse(1000000, 4, torch.bfloat16, 1)}
 
@@ -224,11 +279,39 @@ def master(nwin):
     print(json.dumps(res), flush=True)
 
 
+def scaled(nwin):
+    """The C3 parameter set in fp16: torch's step, the master-weight step and the loss-scaled step."""
+    shapes = param_shapes("c3")
+    nparam = sum(int(torch.Size(s).numel()) for s in shapes)
+    ot, _ = make_optimizer(torch.optim.Adam, shapes, torch.float16)
+    om, _ = make_optimizer(agn_optim.Adam, shapes, torch.float16, master_weights=True)
+    os_, _ = make_optimizer(agn_optim.Adam, shapes, torch.float16, master_weights=True)
+    step, scaler = scaled_step(os_)
+    (tt, tm, ts), spread = windows([ot.step, om.step, step], nwin)
+    assert scaler.steps_skipped() == 0
+    kms, nchunk = kernel_only(om, dtype=torch.float16)
+    cms, sms = scaled_kernels(os_, scaler)
+    res = {"adam_scaled_c3_f16": {"tensors": len(shapes), "params": nparam, "torch_f16_us": tt * 1e6, "master_us": tm * 1e6,
+                                  "scaled_us": ts * 1e6, "scaled_over_master": ts / tm, "torch_over_scaled": tt / ts,
+                                  "torch_minmax_us": [x * 1e6 for x in spread[0]],
+                                  "master_minmax_us": [x * 1e6 for x in spread[1]],
+                                  "scaled_minmax_us": [x * 1e6 for x in spread[2]], "master_kernel_us": kms * 1e3,
+                                  "check_kernel_us": cms * 1e3, "check_GBps": 2.0 * nparam / (cms * 1e-3) / 1e9,
+                                  "scaled_kernel_us": sms * 1e3, "chunks": nchunk}}
+    print(f"adam c3 fp16: {len(shapes)} tensors, {nparam} parameters: torch on the fp16 parameters {tt * 1e6:.1f} us/step, "
+          f"master weights {tm * 1e6:.1f} us/step, LossScaler.step + update {ts * 1e6:.1f} us/step (x{ts / tm:.2f} of the "
+          f"master step, torch x{tt / ts:.2f}); kernels alone: agn_adam_step_master {kms * 1e3:.1f} us, "
+          f"agn_adam_step_master_scaled {sms * 1e3:.1f} us, agn_grad_check {cms * 1e3:.1f} us = "
+          f"{2.0 * nparam / (cms * 1e-3) / 1e9:.0f} GB/s of 2 B/parameter ({nchunk} chunks)", flush=True)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--launch-counts", action="store_true")
     ap.add_argument("--master", action="store_true")
+    ap.add_argument("--scaled", action="store_true")
     ap.add_argument("--child")
     ap.add_argument("--calls", type=int, default=4)
     a = ap.parse_args()
@@ -237,9 +320,12 @@ def main():
     if a.child:
         return child(a.child, a.calls)
     if a.launch_counts:
-        names = [n for n in sorted(tails()) if n.endswith("_c3_bf16") == a.master]
+        group = "_c3_f16" if a.scaled else "_c3_bf16" if a.master else ""
+        names = [n for n in sorted(tails()) if (n.endswith(group) if group else not n.endswith(("_c3_bf16", "_c3_f16")))]
         print(json.dumps({"launches_per_call": launch_counts(names)}), flush=True)
         return
+    if a.scaled:
+        return scaled(a.windows)
     if a.master:
         return master(a.windows)
     res = {}
