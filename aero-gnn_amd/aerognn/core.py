@@ -404,7 +404,10 @@ def edge_forward(*, rows, wpk, bias, ln, e, proj, src, dst, out, a1=None, stats=
 # of a run are read too; an atexit hook waits for the last copy. A copy read
 # inside a backward only records the word: the raise happens at the step boundary (optimizer step,
 # GradAllReduce.__call__, exit). A fault is fatal to the job: under torchrun the raising rank's exit
-# ends the other ranks (they would otherwise wait in the next all-reduce).
+# ends the other ranks (they would otherwise wait in the next all-reduce). At exit nothing can be
+# raised any more (Python prints an exception of an atexit callback and still exits 0), so the hook
+# prints the message, flushes stdout and stderr and ends the process with status 1 (os._exit).
+# The copy and its event go to the caller's current stream, like every launch they cover.
 FAULT_POLL_EVERY = 16
 _fault = {"buf": None, "event": None, "n": 0, "dirty": False, "hooked": False, "word": 0}
 
@@ -459,9 +462,13 @@ def _exit_check():
     try:
         fault_checkpoint(block=True)
     except L.AeroGNNError as exc:
+        # An exception raised in an atexit callback is printed and ignored (exit status 0), so the
+        # status is set here: the message, both streams flushed, then the process ends with 1.
         import sys
         print(f"aerognn: {exc}", file=sys.stderr)
-        raise
+        sys.stdout.flush()
+        sys.stderr.flush()
+        os._exit(1)
 
 
 def _poll_faults():

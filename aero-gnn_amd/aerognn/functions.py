@@ -1159,15 +1159,19 @@ class WecSpec:
             raise NotImplementedError("aerognn WeightedEdgeConv: in_dim 32/64/128, out_dim 64/128, hidden 64")
         self.mod = mod
         p = self.pack = Pack()
-        p.matrix("T", o, i, [(T.weight, 0, 0, False)])
-        p.vector("Tb", o, [(T.bias, 0)])
-        p.matrix("W1", 2 * hd, i, [(W1.weight[:, :i], 0, 0, False), (W1.weight[:, i:2 * i], hd, 0, False)])
-        p.vector("W1b", 2 * hd, [(W1.bias, hd)])
-        p.vector("w1c", hd, [(W1.weight[:, 2 * i], 0)])
-        p.vector("w2", hd + 1, [(W2.weight[0], 0), (W2.bias, hd)])
-        p.matrix("back", i, o + 2 * hd, [(T.weight, 0, 0, True), (W1.weight[:, :i], 0, o, True),
-                                         (W1.weight[:, i:2 * i], 0, o + hd, True)])
-        p.matrix("backT", i, o, [(T.weight, 0, 0, True)])
+        # The column slices are addresses for the packing kernel, taken without a graph: a view that
+        # records one keeps the parameter's gradient accumulator alive, and with it the stream this
+        # spec was built on, where autograd would then accumulate that gradient in every later step.
+        with torch.no_grad():
+            p.matrix("T", o, i, [(T.weight, 0, 0, False)])
+            p.vector("Tb", o, [(T.bias, 0)])
+            p.matrix("W1", 2 * hd, i, [(W1.weight[:, :i], 0, 0, False), (W1.weight[:, i:2 * i], hd, 0, False)])
+            p.vector("W1b", 2 * hd, [(W1.bias, hd)])
+            p.vector("w1c", hd, [(W1.weight[:, 2 * i], 0)])
+            p.vector("w2", hd + 1, [(W2.weight[0], 0), (W2.bias, hd)])
+            p.matrix("back", i, o + 2 * hd, [(T.weight, 0, 0, True), (W1.weight[:, :i], 0, o, True),
+                                             (W1.weight[:, i:2 * i], 0, o + hd, True)])
+            p.matrix("backT", i, o, [(T.weight, 0, 0, True)])
 
     def params(self):
         m = self.mod

@@ -337,11 +337,13 @@ __global__ __launch_bounds__(64 * NW) void dec32_bwd_kernel(const agn_mlp_bwd_ar
 // per-tile LayerNorm partial workspace, grown on demand (device memory kept for the process)
 // LayerNorm partial-row workspace, one per device (a process driving two devices must not
 // share it); a call on another stream than the last user first waits for that stream, which may still
-// be reading it
+// be reading it. `used` says whether there is a last user at all: the null stream (torch's default
+// stream) is a user like any other, so `last` alone cannot say it.
 struct LnScratch {
   float* p = nullptr;
   size_t cap = 0;
   hipStream_t last = nullptr;
+  bool used = false;
 };
 LnScratch g_lnt[64];
 long g_launches = 0;
@@ -378,11 +380,14 @@ bool node32_bwd_try(const agn_mlp_bwd_args* a, void* stream, int* rc, int* ln_ro
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return false;
     LnScratch& w = g_lnt[dev & 63];
-    if (w.last && w.last != st && hipStreamSynchronize(w.last) != hipSuccess) return false;
+    // the last user's node32_lnp_kernel has read the buffer before this call's kernel writes it
+    if (w.used && w.last != st && hipStreamSynchronize(w.last) != hipSuccess) return false;
     const size_t need = (size_t)ntiles * 2 * H;
     if (need > w.cap) {
       if (w.p) {
-        if (hipStreamSynchronize(st) != hipSuccess) return false;
+        // the old buffer is freed after its last user, whichever stream that was (waited for above
+        // when it is not st)
+        if (w.used && hipStreamSynchronize(st) != hipSuccess) return false;
         (void)hipFree(w.p);
         w.p = nullptr;
         w.cap = 0;
@@ -394,6 +399,7 @@ bool node32_bwd_try(const agn_mlp_bwd_args* a, void* stream, int* rc, int* ln_ro
       w.cap = need;
     }
     w.last = st;
+    w.used = true;
     lnt = w.p;
   }
   const int grid = grid_for(ntiles);
