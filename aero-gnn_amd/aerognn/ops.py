@@ -38,9 +38,10 @@ torch.compile / FakeTensorMode, and autograd formulas that are themselves torch.
       cell areas, cell normals, point-to-cell means and the force sums of a 3-D surface given as points and
       a face list, one pass (inference.py:310-320 + utils.py:385-448): agn_surface_forces. No autograd.
   act_dropout(y, act, p, training=True) -> (out like y, keep-mask uint8 [ceil(n / 8)])
-      dropout_p(act(y)) as mlp.py:44-45 applies it between two Linears, act 'relu' / 'gelu' / 'silu' /
-      'tanh' / 'none'; Philox4x32-10 masks at the (seed, offset) of the device's default torch generator,
-      which the call advances (read on the host: not under graph capture): agn_act_dropout_fwd.
+      dropout_p(act(y)) as mlp.py:44-45 applies it between two Linears, act a name of aerognn._lib.ACT
+      ('relu', 'gelu', .. 'tanhshrink': include/aerognn.h AGN_ACT_*) or 'none'; Philox4x32-10 masks at the
+      (seed, offset) of the device's default torch generator, which the call advances (read on the host:
+      not under graph capture): agn_act_dropout_fwd.
       Backward: act_dropout_backward (agn_act_dropout_bwd). ops.act_dropout(...) returns out alone.
 
 The fused MLP / MeshGraphNet-layer kernels are not registered as operators: their calls carry
@@ -337,8 +338,8 @@ torch.library.register_autograd("aerognn::act_dropout", _act_dropout_bwd, setup_
 
 
 def act_dropout(y: Tensor, act: str, p: float, training: bool = True) -> Tensor:
-    """dropout(act(y)) as the reference's MLP applies it between two Linears (mlp.py:44-45): act 'relu' /
-    'gelu' / 'silu' / 'tanh' / 'none', training-mode dropout of probability p on torch's generator.
+    """dropout(act(y)) as the reference's MLP applies it between two Linears (mlp.py:44-45): act a name of
+    aerognn._lib.ACT or 'none', training-mode dropout of probability p on torch's generator.
     torch.ops.aerognn.act_dropout returns the keep-mask bits as well."""
     return torch.ops.aerognn.act_dropout(y, act, p, training)[0]
 

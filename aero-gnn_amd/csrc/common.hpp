@@ -127,17 +127,58 @@ template <> AGN_DEV float lo16<f16>(uint32_t u) { return (float)__builtin_bit_ca
 template <> AGN_DEV float hi16<f16>(uint32_t u) { return (float)__builtin_bit_cast(f16x2, u)[1]; }
 
 // ---------------------------------------------------------------- MLP hidden activations
-// (AGN_ACT_*, mlp.py:37 getattr(F, activation_fn)). fp32 forms of torch's kernels: F.gelu with
-// approximate='none', F.silu, torch.tanh; their backward formulas are torch's GeluBackward,
-// SiluBackward (from the input) and TanhBackward (from the output, rounded as the forward stored it).
+// (AGN_ACT_*, mlp.py:37 getattr(F, activation_fn)). fp32 forms of torch's kernels with their default
+// arguments (ATen Activation.cpp, derivatives.yaml): F.gelu with approximate='none', leaky_relu slope
+// 0.01, elu / celu alpha 1, softplus beta 1 threshold 20. The backward formulas are torch's too, from
+// the input x, with torch's side at every kink; tanh and sigmoid differentiate from the output,
+// rounded as the forward stored it. Nothing overflows for a finite x where torch is finite: every
+// exp is taken of a non-positive argument or feeds a function whose limit at inf is the right value.
+constexpr float SELU_SCALE = 1.0507009873554804934193349852946f;
+constexpr float SELU_NEG = (float)(1.6732632423543772848170429916717 * 1.0507009873554804934193349852946);  // alpha * scale
+constexpr float ONE_SIXTH = 1.0f / 6.0f;  // hardsigmoid's backward multiplies by this (fp64 too: act64.hpp)
+AGN_DEV float sigmoid_f(float x) {
+  // exp of -|x|: 1 / (1 + expf(-x)) would overflow to 1 / inf = 0 below -88.7, where the value is
+  // still a representable subnormal
+  const float e = expf(-fabsf(x));
+  return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+}
+// x - tanh(x). Below 1/8 the difference cancels (tanhf(x) is within an ulp of x), so the odd series
+// x^3/3 - 2x^5/15 + 17x^7/315 - 62x^9/2835 is summed instead (next term < 3e-9 of the first there).
+AGN_DEV float tanhshrink_f(float x) {
+  if (fabsf(x) >= 0.125f) return x - tanhf(x);
+  const float x2 = x * x;
+  const float p = 0.33333333333333333f + x2 * (-0.13333333333333333f + x2 * (0.053968253968253968f + x2 * -0.021869488536155203f));
+  return x * x2 * p;
+}
+// MORE = false: the codes up to AGN_ACT_TANH only. The general MLP kernels instantiate their chains
+// with gelu / silu / tanh on it, so those kernels do not carry the later functions' code (which costs
+// the H = 128 forward kernels some 270 B of scratch per lane and a few others a wave of occupancy).
+template <bool MORE = true>
 AGN_DEV float act_fwd(int k, float x) {
   if (k == AGN_ACT_GELU) return x * 0.5f * (1.f + erff(x * 0.70710678118654752440f));
   if (k == AGN_ACT_SILU) return x / (1.f + expf(-x));
   if (k == AGN_ACT_TANH) return tanhf(x);
-  return fmaxf(x, 0.f);
+  if constexpr (!MORE) return fmaxf(x, 0.f);
+  switch (k) {
+    case AGN_ACT_RELU6: return fminf(fmaxf(x, 0.f), 6.f);
+    case AGN_ACT_HARDTANH: return fminf(fmaxf(x, -1.f), 1.f);
+    case AGN_ACT_LEAKY_RELU: return x > 0.f ? x : x * 0.01f;
+    case AGN_ACT_ELU:
+    case AGN_ACT_CELU: return x > 0.f ? x : expm1f(x);
+    case AGN_ACT_SELU: return x > 0.f ? x * SELU_SCALE : expm1f(x) * SELU_NEG;
+    case AGN_ACT_HARDSIGMOID: return fminf(fmaxf(x + 3.f, 0.f), 6.f) / 6.f;
+    case AGN_ACT_HARDSWISH: return x * fminf(fmaxf(x + 3.f, 0.f), 6.f) / 6.f;
+    case AGN_ACT_SOFTPLUS: return x > 20.f ? x : log1pf(expf(x));
+    case AGN_ACT_SOFTSIGN: return x / (1.f + fabsf(x));
+    case AGN_ACT_SIGMOID: return sigmoid_f(x);
+    case AGN_ACT_LOGSIGMOID: return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
+    case AGN_ACT_MISH: return x * tanhf(x > 20.f ? x : log1pf(expf(x)));
+    case AGN_ACT_TANHSHRINK: return tanhshrink_f(x);
+    default: return fmaxf(x, 0.f);
+  }
 }
 // dy * f'(x), x the (rounded) pre-activation, dy the gradient of the (rounded) output
-template <typename T>
+template <typename T, bool MORE = true>
 AGN_DEV float act_bwd(int k, float x, float dy) {
   if (k == AGN_ACT_GELU) {
     const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
@@ -152,7 +193,45 @@ AGN_DEV float act_bwd(int k, float x, float dy) {
     const float y = round_t<T>(tanhf(x));
     return dy * (1.f - y * y);
   }
-  return x > 0.f ? dy : 0.f;
+  if constexpr (!MORE) return x > 0.f ? dy : 0.f;
+  switch (k) {
+    case AGN_ACT_RELU6: return (x > 0.f && x < 6.f) ? dy : 0.f;
+    case AGN_ACT_HARDTANH: return (x > -1.f && x < 1.f) ? dy : 0.f;
+    case AGN_ACT_LEAKY_RELU: return x > 0.f ? dy : dy * 0.01f;
+    case AGN_ACT_ELU:
+    case AGN_ACT_CELU: return x > 0.f ? dy : dy * expf(x);
+    case AGN_ACT_SELU: return x > 0.f ? dy * SELU_SCALE : dy * SELU_NEG * expf(x);
+    case AGN_ACT_HARDSIGMOID: return (x > -3.f && x < 3.f) ? dy * ONE_SIXTH : 0.f;
+    // (torch 2.10's sides: 0 at -3 itself, dy at 3 itself)
+    case AGN_ACT_HARDSWISH: return x <= -3.f ? 0.f : (x < 3.f ? dy * (x / 3.f + 0.5f) : dy);
+    case AGN_ACT_SOFTPLUS: {
+      if (x > 20.f) return dy;
+      const float z = expf(x);
+      return dy * z / (z + 1.f);
+    }
+    case AGN_ACT_SOFTSIGN: {
+      const float d = 1.f + fabsf(x);
+      return dy / (d * d);
+    }
+    case AGN_ACT_SIGMOID: {
+      const float y = round_t<T>(sigmoid_f(x));
+      return dy * (1.f - y) * y;
+    }
+    case AGN_ACT_LOGSIGMOID: {
+      const float z = expf(-fabsf(x));
+      const float q = z / (1.f + z);
+      return dy * (x < 0.f ? 1.f - q : q);
+    }
+    case AGN_ACT_MISH: {
+      const float t = tanhf(x > 20.f ? x : log1pf(expf(x)));
+      return dy * (t + x * sigmoid_f(x) * (1.f - t * t));
+    }
+    case AGN_ACT_TANHSHRINK: {
+      const float t = tanhf(x);
+      return dy * (t * t);
+    }
+    default: return x > 0.f ? dy : 0.f;
+  }
 }
 
 // o[0..3] = features 16i+4h.., o[4..7] = 16i+8+4h.. (acc registers 8i..8i+7)

@@ -171,7 +171,7 @@ int grid_for(int64_t n) {
   return (int)(need < cap ? need : cap);
 }
 
-bool act_ok(int act) { return act == AGN_ACT_NONE || (act >= AGN_ACT_RELU && act <= AGN_ACT_TANH); }
+bool act_ok(int act) { return act == AGN_ACT_NONE || (act >= AGN_ACT_RELU && act <= AGN_ACT_TANHSHRINK); }
 
 template <typename T>
 void launch_fwd(int64_t n, int act, const void* y, void* out, uint8_t* mask, double p, uint64_t seed, uint64_t offset,

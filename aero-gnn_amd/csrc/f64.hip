@@ -313,6 +313,9 @@ int agn_f64_gemm(const agn_f64_gemm_args* a, void* stream) {
   if (!a || a->rows < 0 || a->n < 1 || a->nseg < 0 || a->nseg > 3 || !a->out) return AGN_E_ARG;
   for (int s = 0; s < a->nseg; ++s)
     if (a->seg[s].k < 0 || (a->seg[s].k > 0 && (!a->seg[s].a || !a->seg[s].w))) return AGN_E_ARG;
+  // relu / mask_act: 0, or 1 + an AGN_ACT_* code
+  if (a->relu < 0 || a->relu > 1 + AGN_ACT_TANHSHRINK || a->mask_act < 0 || a->mask_act > 1 + AGN_ACT_TANHSHRINK)
+    return AGN_E_ARG;
   if (a->rows == 0) return 0;
   const dim3 grid((a->rows + GT - 1) / GT, (a->n + GT - 1) / GT);
   hipLaunchKernelGGL(f64_gemm_kernel, grid, dim3(GTHR), 0, (hipStream_t)stream, *a);

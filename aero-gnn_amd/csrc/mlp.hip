@@ -71,7 +71,7 @@ int fwd_mode(const agn_mlp_fwd_args* a) {
   }
   if (a->nlin > 1 && a->out_dim > a->hidden) return AGN_E_SHAPE;
   if (a->use_ln && a->out_dim > a->hidden) return AGN_E_SHAPE;
-  if (a->act_fn < AGN_ACT_RELU || a->act_fn > AGN_ACT_TANH) return AGN_E_ARG;
+  if (a->act_fn < AGN_ACT_RELU || a->act_fn > AGN_ACT_TANHSHRINK) return AGN_E_ARG;
   for (int l = 0; l < a->nlin; ++l)
     if (!al16(a->act[l]) || !al16(a->pre[l])) return AGN_E_ARG;  // activation buffers are always 16-B accessed
   if (wide) return M_WIDE;  // (never in_full, never M_NIN: always the masked-I/O mode)
@@ -100,7 +100,7 @@ int bwd_mode(const agn_mlp_bwd_args* a) {
     kin += a->din_k[s];
   }
   if (wide && kin > a->in_dim) return AGN_E_SHAPE;  // the blocks index W0^T's packed rows
-  if (a->act_fn < AGN_ACT_RELU || a->act_fn > AGN_ACT_TANH) return AGN_E_ARG;
+  if (a->act_fn < AGN_ACT_RELU || a->act_fn > AGN_ACT_TANHSHRINK) return AGN_E_ARG;
   for (int l = 0; l + 1 < a->nlin; ++l) {
     // the ReLU backward reads the sign bits (AGN_RELU_MASK), the others the saved pre-activation
     if (a->act_fn == AGN_ACT_RELU ? !a->mask[l] : (!a->pre[l] || !al16(a->pre[l]))) return AGN_E_ARG;

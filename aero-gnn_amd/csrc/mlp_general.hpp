@@ -215,7 +215,7 @@ AGN_DEV void walk2_segment(float (&in)[NR], const agn_seg& s, int rr, bool valid
 
 // A hidden activation other than ReLU (AGN_ACT_*): the Linear output rounded to T, saved to pre
 // (the backward's x) when given, the activation applied in fp32 and packed (rounded) into b
-template <typename T, int NT, int NR>
+template <typename T, int NT, int NR, bool MORE>
 AGN_DEV void set_act(BOp<T, NR>& b, const f32x16 (&acc)[NT], int k, T* pre, int tiled, int row, int h, bool valid) {
   constexpr int H = 32 * NT;
   float v[NR];
@@ -228,13 +228,14 @@ AGN_DEV void set_act(BOp<T, NR>& b, const f32x16 (&acc)[NT], int k, T* pre, int 
     else pb.store(pre + (size_t)row * H, h, valid);
   }
 #pragma unroll
-  for (int i = 0; i < NR; ++i) v[i] = act_fwd(k, v[i]);
+  for (int i = 0; i < NR; ++i) v[i] = act_fwd<MORE>(k, v[i]);
   b.set(v);
 }
 
-// GACT: a hidden activation other than ReLU (agn_mlp_*_args.act_fn); the ReLU instantiations
-// carry none of its registers
-template <typename T, int NT, int MODE, bool GACT, bool WIDE = false>
+// GACT: a hidden activation other than ReLU (agn_mlp_*_args.act_fn): 1 = gelu / silu / tanh, 2 = any
+// later code (gact_of); the ReLU instantiations carry none of its registers, and the GACT = 1 ones
+// none of the later functions' code
+template <typename T, int NT, int MODE, int GACT, bool WIDE = false>
 __global__ __launch_bounds__(BLOCK, 2) void mlp_fwd_kernel(const agn_mlp_fwd_args a) {
   static_assert(!WIDE || MODE == M_GEN, "wide segments run on the masked-I/O mode");
   constexpr int H = 32 * NT;
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(BLOCK, 2) void mlp_fwd_kernel(const agn_mlp_fwd_arg
       const int otn = (outl + 31) / 32;
       __syncthreads();
       stage_block(wl, a.wpk[l], NUH, 0, otn, 0, NUH);
-      if constexpr (GACT) set_act<T, NT, NR>(b, acc, a.act_fn, reinterpret_cast<T*>(a.pre[l - 1]), a.tiled, row, h, valid);
+      if constexpr (GACT != 0) set_act<T, NT, NR, GACT == 2>(b, acc, a.act_fn, reinterpret_cast<T*>(a.pre[l - 1]), a.tiled, row, h, valid);
       else b.template set_relu<NT>(acc);
       if (a.act[l - 1]) {
         if (a.tiled) b.store_tiled(reinterpret_cast<T*>(a.act[l - 1]), row, h, valid);
@@ -471,9 +472,10 @@ AGN_DEV void load_grad(float (&g)[NR], const agn_mlp_bwd_args& a, int rr, bool v
   }
 }
 
-// GACT: a hidden activation other than ReLU (agn_mlp_*_args.act_fn); the ReLU instantiations
-// carry none of its registers
-template <typename T, int NT, int MODE, bool GACT, bool WIDE = false>
+// GACT: a hidden activation other than ReLU (agn_mlp_*_args.act_fn): 1 = gelu / silu / tanh, 2 = any
+// later code (gact_of); the ReLU instantiations carry none of its registers, and the GACT = 1 ones
+// none of the later functions' code
+template <typename T, int NT, int MODE, int GACT, bool WIDE = false>
 __global__ __launch_bounds__(BLOCK, 2) void mlp_bwd_kernel(const agn_mlp_bwd_args a) {
   static_assert(!WIDE || MODE == M_GEN, "wide segments run on the masked-I/O mode");
   constexpr bool VEC = (MODE == M_VEC);
@@ -598,7 +600,7 @@ __global__ __launch_bounds__(BLOCK, 2) void mlp_bwd_kernel(const agn_mlp_bwd_arg
         for (int q = 0; q < NR / 4; ++q) {
           const f32x4 x = a.tiled ? load4_tiled<T, NR>(pb, q, rr, h) : load4(pb + (size_t)rr * H + 8 * q + 4 * h);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) A[4 * q + e] = act_bwd<T>(a.act_fn, x[e], round_t<T>(A[4 * q + e]));
+          for (int e = 0; e < 4; ++e) A[4 * q + e] = act_bwd<T, GACT == 2>(a.act_fn, x[e], round_t<T>(A[4 * q + e]));
         }
       }
     } else {
@@ -666,16 +668,19 @@ bool with_const(int v, F&& f) {
   return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
 }
 
+// the kernels' GACT of an AGN_ACT_* code
+inline int gact_of(int act_fn) { return act_fn == AGN_ACT_RELU ? 0 : (act_fn <= AGN_ACT_TANH ? 1 : 2); }
+
 // The one place each direction's general kernel is launched: width, mode and activation become
 // template arguments, and g_last_mode records the instantiation that ran.
 template <typename T>
 int launch_fwd(const agn_mlp_fwd_args& a, int mode, void* stream) {
   const bool ran = with_const<32, 64, 128>(a.hidden, [&](auto hid) {
     with_const<M_VEC, M_GEN, M_NIN, M_NOUT, M_WIDE>(mode, [&](auto m) {
-      with_const<0, 1>(a.act_fn != AGN_ACT_RELU, [&](auto gact) {
+      with_const<0, 1, 2>(gact_of(a.act_fn), [&](auto gact) {
         constexpr bool WIDE = decltype(m)::value == M_WIDE;
         constexpr int MODE = WIDE ? M_GEN : decltype(m)::value;
-        hipLaunchKernelGGL((mlp_fwd_kernel<T, decltype(hid)::value / 32, MODE, decltype(gact)::value != 0, WIDE>),
+        hipLaunchKernelGGL((mlp_fwd_kernel<T, decltype(hid)::value / 32, MODE, decltype(gact)::value, WIDE>),
                            dim3(agn_mlp_bwd_nwaves(a.rows)), dim3(BLOCK), 0, (hipStream_t)stream, a);
         g_last_mode[0] = WIDE ? M_WIDE : MODE;
       });
@@ -688,10 +693,10 @@ template <typename T>
 int launch_bwd(const agn_mlp_bwd_args& a, int mode, void* stream) {
   const bool ran = with_const<32, 64, 128>(a.hidden, [&](auto hid) {
     with_const<M_VEC, M_GEN, M_NOUT, M_WIDE>(mode, [&](auto m) {  // (no narrow-input mode: dX is masked)
-      with_const<0, 1>(a.act_fn != AGN_ACT_RELU, [&](auto gact) {
+      with_const<0, 1, 2>(gact_of(a.act_fn), [&](auto gact) {
         constexpr bool WIDE = decltype(m)::value == M_WIDE;
         constexpr int MODE = WIDE ? M_GEN : decltype(m)::value;
-        hipLaunchKernelGGL((mlp_bwd_kernel<T, decltype(hid)::value / 32, MODE, decltype(gact)::value != 0, WIDE>),
+        hipLaunchKernelGGL((mlp_bwd_kernel<T, decltype(hid)::value / 32, MODE, decltype(gact)::value, WIDE>),
                            dim3(agn_mlp_bwd_nwaves(a.rows)), dim3(BLOCK), 0, (hipStream_t)stream, a);
         g_last_mode[1] = WIDE ? M_WIDE : MODE;
       });

@@ -43,10 +43,20 @@ extern "C" {
 enum { AGN_F32 = 0, AGN_BF16 = 1, AGN_F16 = 2, AGN_F64 = 3 };  /* F64: graph ops and the agn_f64_* entries */
 enum { AGN_SEG_PLAIN = 0, AGN_SEG_GATHER = 1, AGN_SEG_SUM = 2, AGN_SEG_MEAN = 3 };
 enum { AGN_E_ARG = -1, AGN_E_DTYPE = -2, AGN_E_HIDDEN = -3, AGN_E_SHAPE = -4 };
-/* The MLP's hidden activation (mlp.py:37 getattr(F, activation_fn)): ReLU, GELU (exact erf form,
- * F.gelu's default), SiLU, tanh. For 16-bit storage the Linear output is rounded first and the
- * activation applied to the rounded value in fp32, then rounded (the bf16 module's order). */
-enum { AGN_ACT_RELU = 0, AGN_ACT_GELU = 1, AGN_ACT_SILU = 2, AGN_ACT_TANH = 3 };
+/* The MLP's hidden activation (mlp.py:37 getattr(F, activation_fn)): every function of
+ * torch.nn.functional that is elementwise, keeps the shape and takes the input alone, by its name in
+ * lower case (AGN_ACT_LEAKY_RELU = F.leaky_relu), with torch's default arguments: GELU in the exact erf
+ * form, leaky_relu slope 0.01, elu / celu alpha 1, softplus beta 1 and threshold 20, hardtanh on
+ * [-1, 1]. Forward and derivative are torch's formulas, with torch's side at every kink (DESIGN.md
+ * §7h). For 16-bit storage the Linear output is rounded first and the activation applied to the
+ * rounded value in fp32, then rounded (the bf16 module's order). Only ReLU runs on the resident and
+ * the 32-row tile kernels; every other code takes the general kernels. The codes are dense from 0:
+ * an entry point returns AGN_E_ARG for a code outside 0 .. AGN_ACT_TANHSHRINK. */
+enum { AGN_ACT_RELU = 0, AGN_ACT_GELU = 1, AGN_ACT_SILU = 2, AGN_ACT_TANH = 3,
+       AGN_ACT_RELU6 = 4, AGN_ACT_HARDTANH = 5, AGN_ACT_LEAKY_RELU = 6, AGN_ACT_ELU = 7, AGN_ACT_CELU = 8,
+       AGN_ACT_SELU = 9, AGN_ACT_HARDSIGMOID = 10, AGN_ACT_HARDSWISH = 11, AGN_ACT_SOFTPLUS = 12,
+       AGN_ACT_SOFTSIGN = 13, AGN_ACT_SIGMOID = 14, AGN_ACT_LOGSIGMOID = 15, AGN_ACT_MISH = 16,
+       AGN_ACT_TANHSHRINK = 17 };
 
 /* One input segment of a concatenated MLP input row (torch.cat in mgnLayer.py:44,151).
  * PLAIN : row r of ptr;  GATHER: row index[r] of ptr (x[row], x[col] of mgnLayer.py:40-41);
